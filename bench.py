@@ -1,6 +1,8 @@
 """Bench: Ed25519 verifies/s on MI355X (BASELINE.json metric, config C2).
 
     python bench.py [--gpus N --steps K --warmup W]          (N > 1: starts the N ranks itself)
+    python bench.py --full [...]                             (every further measurement and check)
+    python bench.py --dump-outputs DIR [...]                 (the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,10 +21,24 @@ status.  N larger than the visible GPU count is refused (exit 2) unless the
 ranks share GPU 0 (PV_BENCH_SHARE_GPU=1, the gloo rehearsal).
 
 Rank 0 prints ONE JSON line.  `value` = all ranks' verifies / max-over-ranks
-time.  `roofline` prices the dominant (curve) kernel against the measured
-v_mad_u64_u32 issue rate; `cpu_baseline` times libsodium 1.0.18 (the native
-call under Plenum's Verifier.verify) on the host cores, on rank 0 after the
-timed region and the final barrier (every N).
+time; `ms_per_step` = the time of one timed step.  A plain run does only what
+that figure needs: set up, warm up, time the K steps, print the line.
+
+`--full` adds everything else the benchmark measures or checks: the verdicts of
+the measured passes against the synthetic spec (`verdict_mismatches`; exit 3
+on a mismatch), the kernels' own HIP-event durations on sequential calibration
+steps before the timed region, `roofline` (the dominant curve kernel priced
+against the measured v_mad_u64_u32 issue rate), `cpu_baseline` (libsodium
+1.0.18, the native call under Plenum's Verifier.verify, on the host cores, on
+rank 0 after the timed region and the final barrier, every N), the host-buffer
+`end_to_end` and `small_batch_latency` figures and the short runs of the other
+configs.  --no-cpu-baseline, --no-e2e and --no-other-configs trim a --full run.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+returned to its caller as DIR/<name>.npy (float32; rank 0's arrays; an array
+that would take the dump past 64 MB is a fixed, seeded sample of its elements).
+The inputs are a function of the arguments alone, so two builds can be compared
+output for output.
 """
 import argparse
 import ctypes
@@ -381,6 +397,32 @@ def _combined_issue(kernel_rate, peak):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor or array} as path/<name>.npy in float32
+    (every output here is a byte, a small count or a flag: exact in float32).
+    Each array gets an equal share of DUMP_MAX_BYTES; a larger one is written as
+    a fixed sample of its flattened elements (indices drawn once with seed 0 from
+    its size alone, ascending), the same in every run and every build."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) // 4
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float32))
+
+
+def _bitmap_bytes(bitmap):
+    """packed verdict bitmap (int64 words) as its little-endian bytes"""
+    return bitmap.detach().cpu().numpy().view(np.uint8)
+
+
 def cpu_baseline(batch, workload, seconds=1.5, sample=8192):
     """libsodium crypto_sign_verify_detached on the host cores over the first
     `sample` signatures of this rank's workload (copied to host)."""
@@ -581,7 +623,13 @@ def main_c1(args):
         out = authnr.authenticate_batch(reqs, pause_gc=True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    mism = sum(1 for a, b in zip(out, want) if a != b)
+    if args.dump_outputs:
+        # per request: how many identifiers authenticate_batch returned, and whether
+        # they are the request's own (the caller's list of verified identifiers)
+        dump_outputs(args.dump_outputs, {
+            'identifiers': np.array([len(a) if isinstance(a, (list, tuple)) else -1 for a in out]),
+            'authenticated': np.array([a == b for a, b in zip(out, want)])})
+    mism = sum(1 for a, b in zip(out, want) if a != b) if args.full else 0
     value = n * args.steps / elapsed
     res = {
         'metric': METRIC, 'value': round(value, 1), 'unit': 'verifies/s', 'n_gpus': 1, 'steps': args.steps,
@@ -595,7 +643,9 @@ def main_c1(args):
                 'the GPU verify of the batch is a few percent of the step',
         'cpu_baseline': None,
     }
-    if not args.no_cpu_baseline:
+    if not args.full:
+        del res['verdict_mismatches']   # not checked in a plain run
+    if args.full and not args.no_cpu_baseline:
         sv = _sodium_did_verifier()
         base = CoreAuthNr(['buy'], [], [])
         base._verifier = lambda verifier, verkey, idr: verifier(verkey, identifier=idr)  # fresh key per call, as the reference
@@ -691,15 +741,11 @@ def main_bls(args):
         verify_ms += v
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    got = verdict.bool()
-    mism = int((got != expect).sum().item())
-    want_votes = expect.view(nb, nn).sum(1)
-    q_mism = int(((want_votes >= q) != reached.bool()).sum().item()) + int((want_votes != votes).sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'verdict': verdict, 'votes': votes, 'reached': reached})
     value = n * args.steps / elapsed
     verify_ms /= args.steps
     hash_ms /= args.steps
-    peak = _mad_peak()
-    achieved = BLS_W_MAD * n / (verify_ms * 1e-3)
     out = {
         'metric': 'BLS COMMIT checks/sec (verify_sig over AMCL BN254, row f4) on 1 MI355X', 'value': round(value, 1),
         'unit': 'checks/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
@@ -709,8 +755,21 @@ def main_bls(args):
                 '~5% corrupted; parity UNPINNED (ursa absent), verdicts checked against the synthetic spec',
         'config': {'workload': 'C3-BLS: 25-node pool (f=8), {} 3PC batches, every COMMIT BLS-verified + n-f tally'
                    .format(nb), 'name': 'c3bls', 'checks': n, 'batches': nb},
-        'verdict_mismatches': mism, 'quorum_mismatches': q_mism, 'quorums_reached': int(reached.sum().item()),
         'kernel_ms': {'hash': round(hash_ms, 3), 'verify': round(verify_ms, 3)},
+    }
+    if not args.full:
+        if TUNED:
+            out['tuning'] = dict(TUNED)
+        print(json.dumps(out), flush=True)
+        return 0
+    got = verdict.bool()
+    mism = int((got != expect).sum().item())
+    want_votes = expect.view(nb, nn).sum(1)
+    q_mism = int(((want_votes >= q) != reached.bool()).sum().item()) + int((want_votes != votes).sum().item())
+    peak = _mad_peak()
+    achieved = BLS_W_MAD * n / (verify_ms * 1e-3)
+    out.update({
+        'verdict_mismatches': mism, 'quorum_mismatches': q_mism, 'quorums_reached': int(reached.sum().item()),
         'roofline': {'bound': 'valu', 'kernel': 'k_bls_verify_pair (+ k_bls_sigprep)', 'achieved': round(achieved / 1e12, 3),
                      'peak': round(peak / 1e12, 3), 'unit': 'T v_mad lane-ops/s', 'frac': round(achieved / peak, 4),
                      'work_per_check': BLS_W_MAD,
@@ -722,7 +781,7 @@ def main_bls(args):
                              'the one-lane schedule; the lane pair repeats the inversion of the final '
                              'exponentiation on both lanes, not counted); time = the sigma-prep + pair kernels'
                              .format(BLS_W_MUL, BLS_W_SQR)},
-    }
+    })
     # the per-COMMIT regime: host calls of 1 check, one 3PC batch (25 COMMITs,
     # one message) and 10 batches (pv_bls_verify_batch, host buffers)
     sig_h = sig[:250].cpu().numpy()
@@ -794,6 +853,21 @@ def main_f3(args):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'root': root, 'leaves': leaves})
+    if not args.full:
+        res = {
+            'metric': 'Merkle tree hash leaves/sec (ledger TreeHasher.hash_full_tree, SHA-256)',
+            'value': round(n * args.steps / elapsed, 1), 'unit': 'leaves/s', 'n_gpus': 1, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'u32', 'data': 'synthetic random leaves resident in HBM',
+            'config': {'name': 'f3', 'leaves': n, 'leaf_bytes': ln},
+            'input_gbps': round(n * ln * args.steps / elapsed / 1e9, 2),
+        }
+        if TUNED:
+            res['tuning'] = dict(TUNED)
+        print(json.dumps(res), flush=True)
+        return 0
     # the leaf kernel alone, for its roofline: pv_sha256_batch_device over the same
     # leaves (k_sha256, prefix 0x00), HIP events on the launch stream
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -938,7 +1012,7 @@ def other_configs():
         t0 = time.perf_counter()
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), '--config', name, '--steps', str(steps),
-                                '--warmup', str(warm), '--no-cpu-baseline', '--no-e2e'],
+                                '--warmup', str(warm), '--full', '--no-cpu-baseline', '--no-e2e'],
                                capture_output=True, text=True, timeout=300, cwd=REPO)
             line = json.loads(p.stdout.strip().splitlines()[-1]) if p.returncode in (0, 3) and p.stdout.strip() else None
         except (subprocess.TimeoutExpired, ValueError, IndexError) as e:
@@ -1062,8 +1136,15 @@ def main():
                     help='workload (default c2, the headline; f3 = ledger Merkle hashing)')
     ap.add_argument('--n', '--count', dest='n', type=int, default=None,
                     help='signatures per GPU (default: the config\'s); spell it --count under torch.distributed.run')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the host-buffer (PCIe-inclusive) measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure: verdicts against the spec, '
+                         'per-kernel durations and rooflines, the CPU baseline, the host-buffer figures, the other '
+                         'configs (default: set up, warm up, time the steps, print the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy '
+                         '(float32, at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-e2e', action='store_true', help='--full: skip the host-buffer (PCIe-inclusive) measurement')
     ap.add_argument('--key-mod', type=int, default=None,
                     help='experiment: override the config key pool size (keys = i mod N; the line records it)')
     ap.add_argument('--key-format', choices=('auto', 'narrow', 'wide'), default='auto',
@@ -1083,6 +1164,8 @@ def main():
                     help='one stream, each step after the previous one (default: consecutive steps alternate over '
                          'two streams and two workspaces, so step k + 1 starts while step k\'s curve grid drains)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     # --gpus N means N ranks: decided before this process touches the GPU (a
     # self-launch starts fresh children; no exec from a process with a context)
     action, nranks = rank_plan(args.gpus)
@@ -1201,7 +1284,7 @@ def main():
         step()
     torch.cuda.synchronize()
     calib = 0
-    if pipelined:
+    if pipelined and args.full:
         # the kernels' own durations: a few steps one after the other with HIP
         # events on the launch stream, right before the timed region (pipelined
         # launches overlap, so their intervals hold the other stream's work)
@@ -1233,6 +1316,54 @@ def main():
         t = coll_dev(torch.tensor([elapsed], dtype=torch.float64, device=dev))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: its slot's verdicts and packed bitmap
+        # (as bytes), C3's votes and quorum bits, the gathered copies when there are any
+        last = (counter[0] - 1) & 1 if pipelined else 0
+        v_t, b_t, _ = batch.slot_out[last]
+        arrays = {'verdict': v_t, 'bitmap': _bitmap_bytes(b_t)}
+        if tally is not None:
+            arrays.update(votes=tally['votes'][last], reached=tally['reached'][last])
+        if coll:
+            arrays['gathered_bitmap'] = _bitmap_bytes(gathered[last])
+            if tally is not None:
+                arrays['gathered_reached'] = tally['gathered'][last]
+        dump_outputs(args.dump_outputs, arrays)
+    config = {'workload': cfg['workload'], 'name': args.config,
+              'signatures_per_gpu': n, 'msg_bytes': [cfg['mlen'], cfg['mlen_max']] if cfg['mlen'] != cfg['mlen_max']
+              else cfg['mlen'], 'mean_msg_bytes': round(batch.blob_bytes / max(1, n), 1),
+              'key_pool': cfg['key_mod'] or ('node keys' if cfg['mode'] == synth.COMMIT else 'distinct'),
+              'key_cache': 'prepared once per step per distinct key (inside the timed step), {} format'.format(
+                  'wide (radix-256 comb)' if batch.wide else 'narrow (radix-16 comb)') if key_cache else 'off',
+              'parallelism': 'dp{} (disjoint index shards) + {} all-gather of verdict bitmaps'.format(
+                  world, 'RCCL' if backend == 'nccl' else backend + ' (rehearsal, ranks share GPU 0)')
+              if coll else 'single GPU'}
+    schedule = ('pipelined: consecutive steps alternate over 2 streams + 2 verify workspaces/output sets '
+                '(step k + 1 starts while step k drains; all K steps complete inside the timed region)'
+                if pipelined else 'sequential: one stream')
+    if not args.full:
+        # a plain run: the headline figure alone (nothing checked, nothing else measured)
+        out = {
+            'metric': METRIC, 'value': round(world * n * args.steps / elapsed, 1), 'unit': 'verifies/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'u32',
+            'data': 'synthetic (device-generated, deterministic: plenum_gpu/synth.py)',
+            'config': config, 'schedule': schedule,
+        }
+        if tally is not None:
+            config['batches_per_gpu'] = tally['nb']
+            config['quorum'] = tally['q']
+            out['batches_per_s'] = round(world * tally['nb'] * args.steps / elapsed, 1)
+        if rank == 0:
+            if TUNED:
+                out['tuning'] = dict(TUNED)
+            print(json.dumps(out), flush=True)
+        if coll:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # correctness of the measured passes (every output slot): verdict == not
     # tampered, bitmap == verdict, quorum bits == the spec's
@@ -1358,15 +1489,7 @@ def main():
         'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'u32',
         'data': 'synthetic (device-generated, deterministic: plenum_gpu/synth.py)',
-        'config': {'workload': cfg['workload'], 'name': args.config,
-                   'signatures_per_gpu': n, 'msg_bytes': [cfg['mlen'], cfg['mlen_max']] if cfg['mlen'] != cfg['mlen_max']
-                   else cfg['mlen'], 'mean_msg_bytes': round(batch.blob_bytes / max(1, n), 1),
-                   'key_pool': cfg['key_mod'] or ('node keys' if cfg['mode'] == synth.COMMIT else 'distinct'),
-                   'key_cache': 'prepared once per step per distinct key (inside the timed step), {} format'.format(
-                       'wide (radix-256 comb)' if batch.wide else 'narrow (radix-16 comb)') if key_cache else 'off', 'tampered': int(tamper.sum()),
-                   'parallelism': 'dp{} (disjoint index shards) + {} all-gather of verdict bitmaps'.format(
-                       world, 'RCCL' if backend == 'nccl' else backend + ' (rehearsal, ranks share GPU 0)')
-                   if coll else 'single GPU'},
+        'config': dict(config, tampered=int(tamper.sum())),
         'verdict_mismatches': mism,
         'kernel_ms': {'hash': round(ms_hash, 4), 'curve': round(ms_curve, 4), 'timed_on': kernel_ms_on},
         'roofline': {'bound': 'valu', 'kernel': kernel,
@@ -1386,9 +1509,7 @@ def main():
                      'combined_issue': _combined_issue(n / (ms_curve * 1e-3), peak)
                      if (args.config, n) == ('c2', CONFIGS['c2']['n']) and curve_mode == 'half' else None},
         'curve_mode': curve_mode if not key_cache else 'keyed',
-        'schedule': 'pipelined: consecutive steps alternate over 2 streams + 2 verify workspaces/output sets '
-                    '(step k + 1 starts while step k drains; all K steps complete inside the timed region)'
-                    if pipelined else 'sequential: one stream',
+        'schedule': schedule,
         'cpu_baseline': None,
     }
     if key_cache and pipelined:

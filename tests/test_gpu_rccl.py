@@ -46,7 +46,7 @@ def test_bench_loop_with_rccl_collective_at_one_rank():
     """bench.py's N > 1 data path (bitmap + quorum all-gathers on every step's
     stream, max-over-ranks timing, gathered-bytes checks) with RCCL at world 1"""
     p = subprocess.run([sys.executable, '-u', os.path.join(REPO, 'bench.py'), '--config', 'c3', '--n', '250000',
-                        '--steps', '3', '--warmup', '1', '--collective', '--no-cpu-baseline', '--no-e2e'],
+                        '--steps', '3', '--warmup', '1', '--collective', '--full', '--no-cpu-baseline', '--no-e2e'],
                        env=_env(), capture_output=True, text=True, timeout=300, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:] + p.stdout[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -64,7 +64,7 @@ def test_bench_self_launches_two_ranks_gloo_shared_gpu():
            if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(PV_BENCH_BACKEND='gloo', PV_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, '-u', os.path.join(REPO, 'bench.py'), '--gpus', '2', '--config', 'c3',
-                        '--steps', '2', '--warmup', '1', '--no-e2e'],
+                        '--steps', '2', '--warmup', '1', '--full', '--no-e2e'],
                        env=env, capture_output=True, text=True, timeout=420, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:] + p.stdout[-2000:]
     lines = [ln for ln in p.stdout.strip().splitlines() if ln.startswith('{')]

@@ -7,7 +7,7 @@ out=$1; rounds=$2; libs=$3; shift 3
 mkdir -p "$out"
 for r in $(seq 1 "$rounds"); do
   for lib in $libs; do
-    PLENUM_GPU_LIB="$lib" timeout -k 10 300 python bench.py --no-cpu-baseline --no-e2e "$@" > "$out/run.json" 2>> "$out/ab.err" || exit 1
+    PLENUM_GPU_LIB="$lib" timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-e2e "$@" > "$out/run.json" 2>> "$out/ab.err" || exit 1
     python - "$lib" "$out/run.json" "$*" >> "$out/ab.jsonl" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

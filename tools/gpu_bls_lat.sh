@@ -18,6 +18,6 @@ for l in open('$out/lat.tmp'):
     d = json.loads(l); d['lib'] = '$lib'; print(json.dumps(d))" >> "$out/lat.jsonl" || exit 1
   done
 done && cat "$out/lat.jsonl" && \
-PLENUM_GPU_LIB=$cur timeout -k 10 300 python bench.py --config c3bls --no-cpu-baseline > "$out/c3bls_cur.json" 2> "$out/c3bls.err" && \
-PLENUM_GPU_LIB=$other timeout -k 10 300 python bench.py --config c3bls --no-cpu-baseline > "$out/c3bls_other.json" 2>> "$out/c3bls.err" && \
+PLENUM_GPU_LIB=$cur timeout -k 10 300 python bench.py --full --config c3bls --no-cpu-baseline > "$out/c3bls_cur.json" 2> "$out/c3bls.err" && \
+PLENUM_GPU_LIB=$other timeout -k 10 300 python bench.py --full --config c3bls --no-cpu-baseline > "$out/c3bls_other.json" 2>> "$out/c3bls.err" && \
 echo done

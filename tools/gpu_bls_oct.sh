@@ -20,5 +20,5 @@ for l in open('$out/lat.tmp'):
   done
 done
 cat "$out/lat.jsonl"
-timeout -k 10 300 python bench.py --config c3bls --no-cpu-baseline > "$out/c3bls.json" 2> "$out/c3bls.err" && \
+timeout -k 10 300 python bench.py --full --config c3bls --no-cpu-baseline > "$out/c3bls.json" 2> "$out/c3bls.err" && \
 tail -c 250 "$out/c3bls.json" && echo && echo done

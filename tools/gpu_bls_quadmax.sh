@@ -14,6 +14,6 @@ for l in open('$out/lat.tmp'):
     d = json.loads(l); d['lib'] = '$lib'; print(json.dumps(d))" >> "$out/lat.jsonl" || exit 1
 done
 cat "$out/lat.jsonl"
-PLENUM_GPU_LIB=$quad timeout -k 10 300 python bench.py --config c3bls --no-cpu-baseline > "$out/c3bls_quad.json" 2> "$out/c3bls.err" && \
-PLENUM_GPU_LIB=$pair timeout -k 10 300 python bench.py --config c3bls --no-cpu-baseline > "$out/c3bls_pair.json" 2>> "$out/c3bls.err" && \
+PLENUM_GPU_LIB=$quad timeout -k 10 300 python bench.py --full --config c3bls --no-cpu-baseline > "$out/c3bls_quad.json" 2> "$out/c3bls.err" && \
+PLENUM_GPU_LIB=$pair timeout -k 10 300 python bench.py --full --config c3bls --no-cpu-baseline > "$out/c3bls_pair.json" 2>> "$out/c3bls.err" && \
 tail -c 300 "$out/c3bls_quad.json" && echo && tail -c 300 "$out/c3bls_pair.json" && echo done

@@ -10,6 +10,6 @@ out=${1:-gpurun_out/c4km}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for km in 1048576 8192 64; do
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/km$km" -o run -- python3 bench.py --config c4 --key-mod $km \
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/km$km" -o run -- python3 bench.py --full --config c4 --key-mod $km \
       --sequential --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > "$out/km$km.log" 2>&1 || exit 1
 done && echo done

@@ -9,7 +9,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 bash tools/gpu_suite.sh "$out/suite" && \
 echo "[closing] $(date +%T) bench" && \
-timeout -k 10 600 python bench.py > "$out/bench.json" 2> "$out/bench.err" && \
+timeout -k 10 600 python bench.py --full > "$out/bench.json" 2> "$out/bench.err" && \
 echo "[closing] $(date +%T) stats" && \
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/prof_c2" -o run -- python3 bench.py --steps 20 --warmup 5 \
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/prof_c2" -o run -- python3 bench.py --full --steps 20 --warmup 5 \
     --no-cpu-baseline --no-e2e --no-other-configs > "$out/prof_c2.log" 2>&1 && echo "[closing] done"

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_verify.py -x -v --timeout 3
 tail -1 "$out/tests.log"
 for k in 1 2; do
   for f in 1 0; do
-    PV_HOST_FUSED=$f timeout -k 10 300 python bench.py --no-cpu-baseline > "$out/c2_fused$f.$k.json" 2> "$out/c2_fused$f.$k.err" || exit 1
+    PV_HOST_FUSED=$f timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$out/c2_fused$f.$k.json" 2> "$out/c2_fused$f.$k.err" || exit 1
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1]); e=d['end_to_end']; print(sys.argv[1], d['value'], e['value'], e.get('ms'), e['page_locked_inputs']['value'], e.get('verdict_mismatches'))" "$out/c2_fused$f.$k.json"
   done
 done

@@ -13,7 +13,7 @@ grep passed "$out/tests.log"
 for k in 1 2 3; do
   for cfg in 2:32768 3:32768 3:16384 3:8192 2:16384; do
     IFS=: read st r <<< "$cfg"
-    PV_HOST_STREAMS=$st PV_HOST_RAMP=$r timeout -k 10 300 python bench.py --no-cpu-baseline > "$out/c2_$st.$r.$k.json" 2> "$out/c2_$st.$r.$k.err" || exit 1
+    PV_HOST_STREAMS=$st PV_HOST_RAMP=$r timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$out/c2_$st.$r.$k.json" 2> "$out/c2_$st.$r.$k.err" || exit 1
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1]); e=d['end_to_end']; print(sys.argv[1], d['value'], e['value'], e.get('ms'), e['page_locked_inputs']['value'], e.get('verdict_mismatches'))" "$out/c2_$st.$r.$k.json"
   done
 done

@@ -10,8 +10,8 @@ for r in 1 2; do
   for lib in indy-plenum_amd/lib/libplenum_verify.so indy-plenum_amd/lib/ab_hashpf2.so indy-plenum_amd/lib/ab_hashpf4.so; do
     tag=$(basename $lib .so)
     echo "[pf] $(date +%T) $tag $r"
-    PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline > "$out/c4_${tag}_$r.json" 2>/dev/null || exit 1
-    PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-other-configs > "$out/c2_${tag}_$r.json" 2>/dev/null || exit 1
+    PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline > "$out/c4_${tag}_$r.json" 2>/dev/null || exit 1
+    PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-other-configs > "$out/c2_${tag}_$r.json" 2>/dev/null || exit 1
   done
 done
 echo "[pf] done"

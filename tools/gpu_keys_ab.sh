@@ -11,7 +11,7 @@ grep passed "$out/tests_var.log"
 for k in 1 2; do
   for v in default var; do
     if [ $v = var ]; then export PLENUM_GPU_LIB=$PWD/indy-plenum_amd/lib/var_keys3.so; else unset PLENUM_GPU_LIB; fi
-    timeout -k 10 300 python bench.py --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > "$out/c4_$v.$k.json" 2> "$out/c4_$v.$k.err" || exit 1
+    timeout -k 10 300 python bench.py --full --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > "$out/c4_$v.$k.json" 2> "$out/c4_$v.$k.err" || exit 1
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1]); print(sys.argv[1], d['value'], d['ms_per_step'], d['kernel_ms'], d['verdict_mismatches'])" "$out/c4_$v.$k.json"
   done
 done

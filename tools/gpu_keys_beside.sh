@@ -15,8 +15,8 @@ for r in 1 2 3; do
     flag=""
     [ $mode = serial ] && flag="--keys-serial"
     echo "[kb] $(date +%T) $mode $r"
-    timeout -k 10 300 python bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline $flag > "$out/c4_${mode}_$r.json" 2> "$out/c4_${mode}_$r.err" || exit 1
-    timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline $flag > "$out/c3_${mode}_$r.json" 2> "$out/c3_${mode}_$r.err" || exit 1
+    timeout -k 10 300 python bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline $flag > "$out/c4_${mode}_$r.json" 2> "$out/c4_${mode}_$r.err" || exit 1
+    timeout -k 10 300 python bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline $flag > "$out/c3_${mode}_$r.json" 2> "$out/c3_${mode}_$r.err" || exit 1
   done
 done
 echo "[kb] done"

@@ -7,7 +7,7 @@ out=$1; shift
 mkdir -p "$out"
 for r in 1 2; do
   for lib in indy-plenum_amd/lib/libplenum_verify.so "$@"; do
-    PLENUM_GPU_LIB=$lib timeout -k 10 400 python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
+    PLENUM_GPU_LIB=$lib timeout -k 10 400 python bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
       --no-other-configs > "$out/run.json" 2>> "$out/err.log" || exit 1
     python - "$lib" "$out/run.json" >> "$out/ab.jsonl" <<'PY'
 import json, sys

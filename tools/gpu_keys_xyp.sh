@@ -16,10 +16,10 @@ for r in 1 2 3; do
     tag=$(basename $lib .so)
     echo "[kx] $(date +%T) $tag $r"
     if [ $tag != ab_no_tail ]; then
-      PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline > "$out/c4_${tag}_$r.json" 2> "$out/c4_${tag}_$r.err" || exit 1
+      PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline > "$out/c4_${tag}_$r.json" 2> "$out/c4_${tag}_$r.err" || exit 1
     fi
     if [ $tag != ab_keys_xyp ]; then
-      PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --config f3 --steps 5 --warmup 1 --no-cpu-baseline > "$out/f3_${tag}_$r.json" 2> "$out/f3_${tag}_$r.err" || exit 1
+      PLENUM_GPU_LIB=$lib timeout -k 10 300 python bench.py --full --config f3 --steps 5 --warmup 1 --no-cpu-baseline > "$out/f3_${tag}_$r.json" 2> "$out/f3_${tag}_$r.err" || exit 1
     fi
   done
 done
@@ -29,7 +29,7 @@ for lib in indy-plenum_amd/lib/libplenum_verify.so indy-plenum_amd/lib/ab_keys_x
   for pass in FETCH_SIZE WRITE_SIZE; do
     echo "[kx] $(date +%T) pmc $tag $pass"
     PLENUM_GPU_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc $pass --output-format csv -d "$out/pmc_$tag/$pass" -o pmc -- \
-      python3 bench.py --config c4 --steps 1 --warmup 0 --n 2000000 --no-cpu-baseline --no-e2e > "$out/pmc_${tag}_$pass.log" 2>&1 || exit 1
+      python3 bench.py --full --config c4 --steps 1 --warmup 0 --n 2000000 --no-cpu-baseline --no-e2e > "$out/pmc_${tag}_$pass.log" 2>&1 || exit 1
   done
 done
 echo "[kx] done"

@@ -11,7 +11,7 @@ main=indy-plenum_amd/lib/libplenum_verify.so
 bash tools/gpu_suite.sh "$out/suite" && \
 for lib in $main $var; do
   tag=$(basename $lib .so)
-  PLENUM_GPU_LIB=$lib timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/seq_$tag" -o run -- python3 bench.py --steps 10 --warmup 3 \
+  PLENUM_GPU_LIB=$lib timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/seq_$tag" -o run -- python3 bench.py --full --steps 10 --warmup 3 \
     --sequential --no-cpu-baseline --no-e2e --no-other-configs > "$out/seq_$tag.log" 2>&1 || exit 1
 done && \
 bash tools/ab_lib.sh "$out/c2" $main $var 3 --no-other-configs && \

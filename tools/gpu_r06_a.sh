@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 echo tests ok
 timeout -k 10 60 tools/ubench/int_rates > $O/int_rates.json
 echo rates ok
-timeout -k 10 300 python -u bench.py --config c4 --steps 5 --warmup 1 --no-cpu-baseline > $O/c4.json 2> $O/c4.err
+timeout -k 10 300 python -u bench.py --full --config c4 --steps 5 --warmup 1 --no-cpu-baseline > $O/c4.json 2> $O/c4.err
 echo c4 ok
-timeout -k 10 300 python -u bench.py --config c2 --steps 10 --warmup 2 --no-other-configs --no-e2e > $O/c2.json 2> $O/c2.err
+timeout -k 10 300 python -u bench.py --full --config c2 --steps 10 --warmup 2 --no-other-configs --no-e2e > $O/c2.json 2> $O/c2.err
 echo c2 ok

@@ -7,11 +7,11 @@ set -u
 out=${1:-gpurun_out/r06reh}
 mkdir -p "$out"
 echo "[reh] $(date +%T) c2 x4" && \
-PV_BENCH_BACKEND=gloo PV_BENCH_SHARE_GPU=1 timeout -k 10 400 python -u bench.py --gpus 4 --steps 5 --warmup 2 \
+PV_BENCH_BACKEND=gloo PV_BENCH_SHARE_GPU=1 timeout -k 10 400 python -u bench.py --full --gpus 4 --steps 5 --warmup 2 \
     --no-e2e > "$out/c2_n4.json" 2> "$out/c2_n4.err" && \
 echo "[reh] $(date +%T) c4 x2" && \
-PV_BENCH_BACKEND=gloo PV_BENCH_SHARE_GPU=1 timeout -k 10 400 python -u bench.py --gpus 2 --config c4 --steps 3 \
+PV_BENCH_BACKEND=gloo PV_BENCH_SHARE_GPU=1 timeout -k 10 400 python -u bench.py --full --gpus 2 --config c4 --steps 3 \
     --warmup 1 --n 2000000 --no-cpu-baseline > "$out/c4_n2.json" 2> "$out/c4_n2.err" && \
 echo "[reh] $(date +%T) c3" && \
-timeout -k 10 300 python -u bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline > "$out/c3.json" 2> "$out/c3.err" && \
+timeout -k 10 300 python -u bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline > "$out/c3.json" 2> "$out/c3.err" && \
 echo "[reh] done"

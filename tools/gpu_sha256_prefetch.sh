@@ -10,7 +10,7 @@ timeout -k 10 300 python -u -m pytest -x -v --timeout 200 --timeout-method threa
 for r in 1 2 3; do
   for lib in indy-plenum_amd/lib/libplenum_verify.so indy-plenum_amd/lib/ab_sha_noprefetch.so; do
     tag=$(basename $lib .so)
-    PLENUM_GPU_LIB=$lib timeout -k 10 200 python bench.py --config f3 --steps 5 --warmup 1 > "$out/f3_${tag}_$r.json" 2>/dev/null || exit 1
+    PLENUM_GPU_LIB=$lib timeout -k 10 200 python bench.py --full --config f3 --steps 5 --warmup 1 > "$out/f3_${tag}_$r.json" 2>/dev/null || exit 1
   done
 done
 echo done

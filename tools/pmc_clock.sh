@@ -9,6 +9,6 @@ for lib in "$@"; do
   tag=$(basename "$lib" .so)
   PLENUM_GPU_LIB=$(realpath "$lib") timeout -s KILL 90 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT SQ_BUSY_CYCLES SQ_WAVES \
       --output-format csv -d "$out/$tag" -o pmc -- \
-      python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > "$out/$tag.log" 2>&1 || exit 1
+      python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > "$out/$tag.log" 2>&1 || exit 1
   echo "pass $tag ok"
 done
