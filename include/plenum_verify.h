@@ -232,6 +232,97 @@ int pv_merkle_root(const uint8_t *blob, const uint64_t *off, uint64_t n, uint8_t
 int pv_merkle_root_device(const uint8_t *blob, const uint64_t *off, uint64_t n, uint8_t *leaf_hashes, uint8_t *root,
                           int device, void *stream);
 
+/* Merkle audit paths and consistency proofs, batched (one proof per GPU lane).
+ * All digests are 32 bytes; indices and sizes are 64-bit.  Proof nodes of a
+ * batch lie in one array `nodes`; proof i is nodes[proof_off[i] .. proof_off[i+1])
+ * (proof_off: n + 1 entries, counted in nodes, monotone).
+ *
+ * Per-proof status (status[i], one byte each): */
+#define PV_MP_OK 0
+#define PV_MP_BAD_RANGE 1      /* index >= tree_size, or old_size > new_size (the reference's ValueError) */
+#define PV_MP_TOO_SHORT 2      /* ProofError: proof too short */
+#define PV_MP_TOO_LONG 3       /* ProofError: proof too long (inclusion only) */
+#define PV_MP_ROOT_MISMATCH 4  /* ProofError: computed root (consistency: the new root) differs */
+#define PV_MP_INCONSISTENT 5   /* ConsistencyError: the old root differs, or equal sizes with different roots */
+/* len_out[i] of a request the *_device generation entries refuse */
+#define PV_MP_LEN_REFUSED 0xffffffffu
+
+/*   pv_merkle_verify_inclusion[_device]
+ *       MerkleVerifier.verify_leaf_hash_inclusion / verify_leaf_inclusion
+ *       (ledger/merkle_verifier.py:155-266) for n proofs.  Leaves: leaf_hashes (n x 32), or,
+ *       when leaf_hashes is NULL, the leaf data leaf_blob / leaf_off (n + 1 offsets), hashed
+ *       on the GPU as SHA-256(0x00 || leaf) first.  Proof i's root is roots[i], or
+ *       roots[root_idx[i]] of a table of n_roots roots when root_idx is not NULL.
+ *       Out: status[i]; computed[i] = the root the walk reached; stop_index[i] = the node
+ *       index a too-short walk stopped at (the reference's message prints it), else 0.
+ *   pv_merkle_verify_consistency[_device]
+ *       MerkleVerifier.verify_tree_consistency (:47-153) for n (old_size, new_size) pairs,
+ *       the same order of decisions: equal sizes compare roots; old_size == 0 passes; "new
+ *       root differs" wins over "old root differs"; extra nodes are accepted.  Roots as
+ *       above (old_root_idx / new_root_idx both NULL or both given; then old_roots and
+ *       new_roots are tables of n_roots entries and may be the same table).
+ *       Out: status[i], old_computed[i], new_computed[i] (the given roots when the proof is
+ *       not walked).
+ * Host forms check proof_off, leaf_off and the root indices (PV_EINVAL).  Device forms take
+ * DEVICE buffers, 16-byte aligned digests, each root index < n_roots (not checked), and a
+ * leaf blob with >= 16 readable bytes after the last leaf. */
+int pv_merkle_verify_inclusion(const uint8_t *leaf_hashes, const uint8_t *leaf_blob, const uint64_t *leaf_off,
+                               const uint64_t *index, const uint64_t *tree_size, const uint8_t *nodes,
+                               const uint64_t *proof_off, const uint8_t *roots, const uint32_t *root_idx,
+                               uint64_t n_roots, uint64_t n, uint8_t *status, uint8_t *computed,
+                               uint64_t *stop_index);
+int pv_merkle_verify_inclusion_device(const uint8_t *leaf_hashes, const uint8_t *leaf_blob, const uint64_t *leaf_off,
+                                      const uint64_t *index, const uint64_t *tree_size, const uint8_t *nodes,
+                                      const uint64_t *proof_off, const uint8_t *roots, const uint32_t *root_idx,
+                                      uint64_t n_roots, uint64_t n, uint8_t *status, uint8_t *computed,
+                                      uint64_t *stop_index, int device, void *stream);
+int pv_merkle_verify_consistency(const uint64_t *old_size, const uint64_t *new_size, const uint8_t *old_roots,
+                                 const uint8_t *new_roots, const uint32_t *old_root_idx, const uint32_t *new_root_idx,
+                                 uint64_t n_roots, const uint8_t *nodes, const uint64_t *proof_off, uint64_t n,
+                                 uint8_t *status, uint8_t *old_computed, uint8_t *new_computed);
+int pv_merkle_verify_consistency_device(const uint64_t *old_size, const uint64_t *new_size, const uint8_t *old_roots,
+                                        const uint8_t *new_roots, const uint32_t *old_root_idx,
+                                        const uint32_t *new_root_idx, uint64_t n_roots, const uint8_t *nodes,
+                                        const uint64_t *proof_off, uint64_t n, uint8_t *status, uint8_t *old_computed,
+                                        uint8_t *new_computed, int device, void *stream);
+
+/* Device-resident Merkle tree with every level kept: the read side of
+ * CompactMerkleTree (ledger/compact_merkle_tree.py:197-249) for batches.
+ *   pv_merkle_tree_create        an empty tree on `device` (capacity_hint leaves allocated up
+ *                                front; capacity doubles on overflow); *handle > 0
+ *   pv_merkle_tree_extend        append k leaves (HOST blob / off, hashed as SHA-256(0x00 || leaf));
+ *                                CompactMerkleTree.extend / append
+ *   pv_merkle_tree_extend_hashes[_device]  append k leaf hashes (k x 32, HOST / DEVICE memory)
+ *   pv_merkle_tree_info          *n leaves, *depth levels above them, root = MTH(0, n)
+ *                                (CompactMerkleTree.root_hash; SHA-256("") for n = 0)
+ *   pv_merkle_tree_free          release it (pv_shutdown releases every tree)
+ *   pv_merkle_audit_paths[_device]
+ *       CompactMerkleTree.inclusion_proof(index[i], tree_size[i]) and merkle_tree_hash(0,
+ *       tree_size[i]) (what Ledger.merkleInfo / auditProof read, ledger/ledger.py:196-217) for k
+ *       requests.  Request i's path is nodes_out[i * (depth + 1) * 32 ...], len_out[i] nodes,
+ *       bottom-up; roots_out[i] = MTH(0, tree_size[i]).
+ *   pv_merkle_consistency_proofs[_device]
+ *       CompactMerkleTree.consistency_proof(first[i], second[i]) (seeder_service.py:85,103),
+ *       same output layout; empty for first == 0 and first == second.
+ * A request with index >= tree_size, tree_size == 0, tree_size > n, first > second or
+ * second > n is never clamped: the host forms return PV_EINVAL before any launch; the device
+ * forms (request arrays in DEVICE memory) write len_out[i] = PV_MP_LEN_REFUSED and nothing
+ * else for it.  A freed or foreign handle is PV_EINVAL. */
+int pv_merkle_tree_create(uint64_t capacity_hint, int device, int32_t *handle);
+int pv_merkle_tree_extend(int32_t handle, const uint8_t *blob, const uint64_t *off, uint64_t k);
+int pv_merkle_tree_extend_hashes(int32_t handle, const uint8_t *leaf_hashes, uint64_t k);
+int pv_merkle_tree_extend_hashes_device(int32_t handle, const uint8_t *leaf_hashes, uint64_t k, void *stream);
+int pv_merkle_tree_info(int32_t handle, uint64_t *n, uint32_t *depth, uint8_t *root);
+int pv_merkle_tree_free(int32_t handle);
+int pv_merkle_audit_paths(int32_t handle, const uint64_t *index, const uint64_t *tree_size, uint64_t k,
+                          uint8_t *nodes_out, uint32_t *len_out, uint8_t *roots_out);
+int pv_merkle_audit_paths_device(int32_t handle, const uint64_t *index, const uint64_t *tree_size, uint64_t k,
+                                 uint8_t *nodes_out, uint32_t *len_out, uint8_t *roots_out, void *stream);
+int pv_merkle_consistency_proofs(int32_t handle, const uint64_t *first, const uint64_t *second, uint64_t k,
+                                 uint8_t *nodes_out, uint32_t *len_out);
+int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t *first, const uint64_t *second, uint64_t k,
+                                        uint8_t *nodes_out, uint32_t *len_out, void *stream);
+
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of
  *                 batch b = node 32 w + j cast a valid vote in batch b (a voter SET:

@@ -509,6 +509,7 @@ struct DeviceGuard {
 
 std::mutex g_mu;
 std::vector<Device> g_devs;
+void release_trees();   // resident Merkle trees (pv_merkle_tree_*), below
 
 Device* find_dev(int id) {
   for (auto& d : g_devs)
@@ -1420,6 +1421,7 @@ int pv_test_set_spin_ns(int64_t ns) {
 void pv_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_mu);
   DeviceGuard dg;
+  release_trees();
   for (auto& d : g_devs) release_device(d);
   g_devs.clear();
   g_kc.clear();
@@ -2170,6 +2172,542 @@ int pv_sha256_batch(const uint8_t* blob, const uint64_t* off, uint64_t n, int32_
   HIP_OK(hipMemcpyAsync(digests, d.mk0.p, n * 32, hipMemcpyDeviceToHost, d.stream));
   HIP_OK(hipStreamSynchronize(d.stream));
   return PV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------ Merkle audit paths / consistency
+namespace {
+
+// call-scoped device buffer of the host-buffer entry points
+template <typename T>
+struct TmpBuf {
+  T* p = nullptr;
+  TmpBuf() = default;
+  TmpBuf(const TmpBuf&) = delete;
+  TmpBuf& operator=(const TmpBuf&) = delete;
+  ~TmpBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
+  // allocate and start the upload of n elements on s
+  hipError_t put(const T* host, size_t n, hipStream_t s) {
+    hipError_t e = alloc(n);
+    if (e != hipSuccess || n == 0) return e;
+    return hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s);
+  }
+};
+
+inline const uint32_t* w32(const uint8_t* p) { return reinterpret_cast<const uint32_t*>(p); }
+inline uint32_t* w32(uint8_t* p) { return reinterpret_cast<uint32_t*>(p); }
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+int merkle_blocks(const Device& d) { return d.cu_count * 32; }
+
+// A resident tree: one device buffer per level (level 0 = leaf hashes, an odd
+// last node moves up), capacities geometric, plus the device table of level
+// pointers the generation kernels read.
+constexpr uint32_t MT_LEVELS = 65;
+struct MerkleTree {
+  bool live = false;
+  int dev = -1;           // Device::id
+  uint64_t n = 0;         // leaves
+  uint32_t depth = 0;     // levels above the leaves
+  uint64_t hint = 1;
+  std::vector<uint32_t*> lv;
+  std::vector<uint64_t> cap;   // nodes
+  const uint32_t** table = nullptr;   // device: MT_LEVELS level pointers
+  std::vector<const uint32_t*> host_table;
+  bool dirty = true;
+};
+std::vector<MerkleTree> g_trees;   // handle = index + 1
+
+void tree_release(MerkleTree& t) {
+  if (!t.live) return;
+  if (Device* d = find_dev(t.dev)) {
+    (void)hipSetDevice(d->ord);
+    (void)hipStreamSynchronize(d->stream);
+  }
+  for (uint32_t* p : t.lv)
+    if (p) (void)hipFree(p);
+  if (t.table) (void)hipFree(t.table);
+  t = MerkleTree();
+}
+
+void release_trees() {
+  for (auto& t : g_trees) tree_release(t);
+  g_trees.clear();
+}
+
+MerkleTree* find_tree(int32_t handle) {
+  if (handle < 1 || (size_t)handle > g_trees.size() || !g_trees[handle - 1].live) return nullptr;
+  return &g_trees[handle - 1];
+}
+
+uint64_t level_count(uint64_t n, uint32_t l) { return n == 0 ? 0 : ((n - 1) >> l) + 1; }
+
+// level l holds at least `need` nodes afterwards; on overflow the capacity
+// doubles and the nodes in use are copied device-to-device on s
+int tree_grow(MerkleTree& t, uint32_t l, uint64_t need, hipStream_t s) {
+  if (l >= MT_LEVELS) return fail(PV_EINVAL, "Merkle tree deeper than %u levels", MT_LEVELS - 1);
+  if (l >= t.lv.size()) {
+    t.lv.resize(l + 1, nullptr);
+    t.cap.resize(l + 1, 0);
+  }
+  if (need <= t.cap[l]) return PV_OK;
+  uint64_t nc = t.cap[l];
+  if (nc == 0) {
+    nc = l < 64 ? ((t.hint - 1) >> l) + 1 : 1;
+  }
+  while (nc < need) nc *= 2;
+  uint32_t* np = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void**>(&np), nc * 32));
+  uint64_t used = l <= t.depth ? level_count(t.n, l) : 0;
+  if (used > t.cap[l]) used = t.cap[l];
+  if (t.lv[l]) {
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(np, t.lv[l], used * 32, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipFree(np);
+      HIP_OK(e);
+    }
+    (void)hipFree(t.lv[l]);
+  }
+  t.lv[l] = np;
+  t.cap[l] = nc;
+  t.dirty = true;
+  return PV_OK;
+}
+
+// leaves n .. n + k - 1 are in level 0: rebuild the parents they change.  At
+// level l + 1 the first changed parent is n_old >> (l + 1) (the old promoted
+// right-edge node is recomputed); levels are added as the tree deepens.
+int tree_rebuild(MerkleTree& t, uint64_t n_new, hipStream_t s) {
+  const uint64_t n_old = t.n;
+  uint64_t m = n_new;
+  uint32_t l = 0;
+  while (m > 1) {
+    const uint64_t outs = (m + 1) / 2;
+    int rc = tree_grow(t, l + 1, outs, s);
+    if (rc) return rc;
+    HIP_OK(pv::launch_merkle_level_keep(t.lv[l], l + 1 < 64 ? n_old >> (l + 1) : 0, m, t.lv[l + 1], s));
+    m = outs;
+    ++l;
+  }
+  t.depth = l;
+  t.n = n_new;
+  if (t.dirty) {
+    if (!t.table) HIP_OK(hipMalloc(reinterpret_cast<void**>(&t.table), MT_LEVELS * sizeof(uint32_t*)));
+    t.host_table.assign(MT_LEVELS, nullptr);
+    for (size_t i = 0; i < t.lv.size(); ++i) t.host_table[i] = t.lv[i];
+    HIP_OK(hipMemcpyAsync(t.table, t.host_table.data(), MT_LEVELS * sizeof(uint32_t*), hipMemcpyHostToDevice, s));
+    t.dirty = false;
+  }
+  return PV_OK;
+}
+
+// resolve a handle to its tree and device, and make the device current
+int tree_enter(int32_t handle, MerkleTree** t, Device** d) {
+  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  *t = find_tree(handle);
+  if (!*t) return fail(PV_EINVAL, "no Merkle tree with handle %d", (int)handle);
+  *d = find_dev((*t)->dev);
+  if (!*d) return fail(PV_EINVAL, "the device of Merkle tree %d is gone", (int)handle);
+  HIP_OK(hipSetDevice((*d)->ord));
+  return PV_OK;
+}
+
+int offsets_ok(const uint64_t* off, uint64_t n, const char* what) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(PV_EINVAL, "%s not monotone at %llu", what, (unsigned long long)i);
+  return PV_OK;
+}
+
+// all device memory; leaf = leaf hashes, or NULL: hash blob / off into d.mk0 first
+int enqueue_verify_incl(Device& d, const uint32_t* leaf, const uint8_t* blob, const uint64_t* off,
+                        const uint64_t* index, const uint64_t* tree_size, const uint32_t* nodes,
+                        const uint64_t* proof_off, const uint32_t* roots, const uint32_t* root_idx, uint64_t n,
+                        uint8_t* status, uint32_t* computed, uint64_t* stop_index, hipStream_t s) {
+  if (!leaf) {   // leaf mode: the existing leaf hasher, then the walk
+    HIP_OK(d.mk0.ensure(n * 8));
+    HIP_OK(pv::launch_sha256(blob, off, n, 1, 0x00, d.counter.p, d.mk0.p, d.sha256_blocks, s));
+    leaf = d.mk0.p;
+  }
+  HIP_OK(pv::launch_merkle_verify_incl(leaf, index, tree_size, nodes, proof_off, roots, root_idx, n, status, computed,
+                                       stop_index, merkle_blocks(d), s));
+  return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pv_merkle_verify_inclusion_device(const uint8_t* leaf_hashes, const uint8_t* leaf_blob, const uint64_t* leaf_off,
+                                      const uint64_t* index, const uint64_t* tree_size, const uint8_t* nodes,
+                                      const uint64_t* proof_off, const uint8_t* roots, const uint32_t* root_idx,
+                                      uint64_t n_roots, uint64_t n, uint8_t* status, uint8_t* computed,
+                                      uint64_t* stop_index, int device, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  Device* d = find_dev(device);
+  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (n == 0) return PV_OK;
+  if ((!leaf_hashes && (!leaf_blob || !leaf_off)) || !index || !tree_size || !nodes || !proof_off || !roots ||
+      !status || !computed || !stop_index)
+    return fail(PV_EINVAL, "null device buffer");
+  if (root_idx && n_roots == 0) return fail(PV_EINVAL, "root_idx without roots");
+  if (misaligned16(leaf_hashes) || misaligned16(nodes) || misaligned16(roots) || misaligned16(computed))
+    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  HIP_OK(hipSetDevice(d->ord));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  int rc = enqueue_verify_incl(*d, w32(leaf_hashes), leaf_blob, leaf_off, index, tree_size, w32(nodes), proof_off,
+                               w32(roots), root_idx, n, status, w32(computed), stop_index, s);
+  if (rc) return rc;
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_verify_inclusion(const uint8_t* leaf_hashes, const uint8_t* leaf_blob, const uint64_t* leaf_off,
+                               const uint64_t* index, const uint64_t* tree_size, const uint8_t* nodes,
+                               const uint64_t* proof_off, const uint8_t* roots, const uint32_t* root_idx,
+                               uint64_t n_roots, uint64_t n, uint8_t* status, uint8_t* computed,
+                               uint64_t* stop_index) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  if (n == 0) return PV_OK;
+  if ((!leaf_hashes && !leaf_off) || !index || !tree_size || !proof_off || !roots || !status || !computed ||
+      !stop_index)
+    return fail(PV_EINVAL, "null buffer");
+  int rc = offsets_ok(proof_off, n, "proof_off");
+  if (rc) return rc;
+  const uint64_t p0 = proof_off[0], total = proof_off[n] - p0;
+  if (total && !nodes) return fail(PV_EINVAL, "null buffer");
+  uint64_t b0 = 0, bytes = 0;
+  if (!leaf_hashes) {
+    rc = offsets_ok(leaf_off, n, "leaf_off");
+    if (rc) return rc;
+    b0 = leaf_off[0];
+    bytes = leaf_off[n] - b0;
+    if (bytes && !leaf_blob) return fail(PV_EINVAL, "null buffer");
+  }
+  if (root_idx)
+    for (uint64_t i = 0; i < n; ++i)
+      if (root_idx[i] >= n_roots)
+        return fail(PV_EINVAL, "root_idx[%llu] = %u is not below n_roots %llu", (unsigned long long)i, root_idx[i],
+                    (unsigned long long)n_roots);
+  Device& d = g_devs[0];
+  HIP_OK(hipSetDevice(d.ord));
+  hipStream_t s = d.stream;
+  std::vector<uint64_t> poff(n + 1), loff;
+  for (uint64_t i = 0; i <= n; ++i) poff[i] = proof_off[i] - p0;
+  TmpBuf<uint8_t> dleaf, dblob, dnodes, droots, dstatus, dcomp;
+  TmpBuf<uint64_t> dloff, dindex, dsize, dpoff, dstop;
+  TmpBuf<uint32_t> dridx;
+  if (leaf_hashes) {
+    HIP_OK(dleaf.put(leaf_hashes, n * 32, s));
+  } else {
+    loff.resize(n + 1);
+    for (uint64_t i = 0; i <= n; ++i) loff[i] = leaf_off[i] - b0;
+    HIP_OK(dblob.alloc(bytes + 16));
+    if (bytes) HIP_OK(hipMemcpyAsync(dblob.p, leaf_blob + b0, bytes, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(dblob.p + bytes, 0, 16, s));
+    HIP_OK(dloff.put(loff.data(), n + 1, s));
+  }
+  HIP_OK(dindex.put(index, n, s));
+  HIP_OK(dsize.put(tree_size, n, s));
+  HIP_OK(dnodes.put(total ? nodes + p0 * 32 : nullptr, total * 32, s));
+  HIP_OK(dpoff.put(poff.data(), n + 1, s));
+  HIP_OK(droots.put(roots, (root_idx ? n_roots : n) * 32, s));
+  if (root_idx) HIP_OK(dridx.put(root_idx, n, s));
+  HIP_OK(dstatus.alloc(n));
+  HIP_OK(dcomp.alloc(n * 32));
+  HIP_OK(dstop.alloc(n));
+  rc = enqueue_verify_incl(d, leaf_hashes ? w32(dleaf.p) : nullptr, dblob.p, dloff.p, dindex.p, dsize.p,
+                           w32(dnodes.p), dpoff.p, w32(droots.p), dridx.p, n, dstatus.p, w32(dcomp.p), dstop.p, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  HIP_OK(hipMemcpyAsync(status, dstatus.p, n, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(computed, dcomp.p, n * 32, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(stop_index, dstop.p, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_verify_consistency_device(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
+                                        const uint8_t* new_roots, const uint32_t* old_root_idx,
+                                        const uint32_t* new_root_idx, uint64_t n_roots, const uint8_t* nodes,
+                                        const uint64_t* proof_off, uint64_t n, uint8_t* status, uint8_t* old_computed,
+                                        uint8_t* new_computed, int device, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  Device* d = find_dev(device);
+  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (n == 0) return PV_OK;
+  if (!old_size || !new_size || !old_roots || !new_roots || !nodes || !proof_off || !status || !old_computed ||
+      !new_computed)
+    return fail(PV_EINVAL, "null device buffer");
+  if ((old_root_idx == nullptr) != (new_root_idx == nullptr))
+    return fail(PV_EINVAL, "old_root_idx and new_root_idx go together");
+  if (old_root_idx && n_roots == 0) return fail(PV_EINVAL, "root indices without roots");
+  if (misaligned16(old_roots) || misaligned16(new_roots) || misaligned16(nodes) || misaligned16(old_computed) ||
+      misaligned16(new_computed))
+    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  HIP_OK(hipSetDevice(d->ord));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  HIP_OK(pv::launch_merkle_verify_cons(old_size, new_size, w32(old_roots), w32(new_roots), old_root_idx, new_root_idx,
+                                       w32(nodes), proof_off, n, status, w32(old_computed), w32(new_computed),
+                                       merkle_blocks(*d), s));
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
+                                 const uint8_t* new_roots, const uint32_t* old_root_idx, const uint32_t* new_root_idx,
+                                 uint64_t n_roots, const uint8_t* nodes, const uint64_t* proof_off, uint64_t n,
+                                 uint8_t* status, uint8_t* old_computed, uint8_t* new_computed) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  if (n == 0) return PV_OK;
+  if (!old_size || !new_size || !old_roots || !new_roots || !proof_off || !status || !old_computed || !new_computed)
+    return fail(PV_EINVAL, "null buffer");
+  if ((old_root_idx == nullptr) != (new_root_idx == nullptr))
+    return fail(PV_EINVAL, "old_root_idx and new_root_idx go together");
+  int rc = offsets_ok(proof_off, n, "proof_off");
+  if (rc) return rc;
+  const uint64_t p0 = proof_off[0], total = proof_off[n] - p0;
+  if (total && !nodes) return fail(PV_EINVAL, "null buffer");
+  if (old_root_idx)
+    for (uint64_t i = 0; i < n; ++i)
+      if (old_root_idx[i] >= n_roots || new_root_idx[i] >= n_roots)
+        return fail(PV_EINVAL, "a root index of pair %llu is not below n_roots %llu", (unsigned long long)i,
+                    (unsigned long long)n_roots);
+  Device& d = g_devs[0];
+  HIP_OK(hipSetDevice(d.ord));
+  hipStream_t s = d.stream;
+  std::vector<uint64_t> poff(n + 1);
+  for (uint64_t i = 0; i <= n; ++i) poff[i] = proof_off[i] - p0;
+  const uint64_t nr = old_root_idx ? n_roots : n;
+  TmpBuf<uint8_t> dnodes, dro, drn, dstatus, dco, dcn;
+  TmpBuf<uint64_t> dold, dnew, dpoff;
+  TmpBuf<uint32_t> dio, din;
+  HIP_OK(dold.put(old_size, n, s));
+  HIP_OK(dnew.put(new_size, n, s));
+  HIP_OK(dro.put(old_roots, nr * 32, s));
+  HIP_OK(drn.put(new_roots, nr * 32, s));
+  if (old_root_idx) {
+    HIP_OK(dio.put(old_root_idx, n, s));
+    HIP_OK(din.put(new_root_idx, n, s));
+  }
+  HIP_OK(dnodes.put(total ? nodes + p0 * 32 : nullptr, total * 32, s));
+  HIP_OK(dpoff.put(poff.data(), n + 1, s));
+  HIP_OK(dstatus.alloc(n));
+  HIP_OK(dco.alloc(n * 32));
+  HIP_OK(dcn.alloc(n * 32));
+  HIP_OK(pv::launch_merkle_verify_cons(dold.p, dnew.p, w32(dro.p), w32(drn.p), dio.p, din.p, w32(dnodes.p), dpoff.p, n,
+                                       dstatus.p, w32(dco.p), w32(dcn.p), merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(status, dstatus.p, n, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(old_computed, dco.p, n * 32, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(new_computed, dcn.p, n * 32, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_tree_create(uint64_t capacity_hint, int device, int32_t* handle) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  if (!handle) return fail(PV_EINVAL, "null pointer");
+  Device* d = find_dev(device);
+  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (capacity_hint > (1ull << 40)) return fail(PV_EINVAL, "capacity_hint above 2^40 leaves");
+  size_t slot = 0;
+  while (slot < g_trees.size() && g_trees[slot].live) ++slot;
+  if (slot == g_trees.size()) {
+    if (g_trees.size() >= 0x7fffffffull) return fail(PV_ENOMEM, "too many Merkle trees");
+    g_trees.emplace_back();
+  }
+  MerkleTree& t = g_trees[slot];
+  t = MerkleTree();
+  t.live = true;
+  t.dev = d->id;
+  t.hint = capacity_hint ? capacity_hint : 1;
+  HIP_OK(hipSetDevice(d->ord));
+  int rc = tree_grow(t, 0, t.hint, d->stream);
+  if (rc == PV_OK) rc = tree_rebuild(t, 0, d->stream);   // uploads the level table
+  if (rc == PV_OK) {
+    hipError_t e = hipStreamSynchronize(d->stream);
+    if (e != hipSuccess) rc = fail(PV_EIO, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+  }
+  if (rc) {
+    tree_release(t);
+    return rc;
+  }
+  *handle = (int32_t)(slot + 1);
+  return PV_OK;
+}
+
+int pv_merkle_tree_free(int32_t handle) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  MerkleTree* t = find_tree(handle);
+  if (!t) return fail(PV_EINVAL, "no Merkle tree with handle %d", (int)handle);
+  tree_release(*t);
+  return PV_OK;
+}
+
+// append k leaf hashes from host or device memory and rebuild the parents they change
+static int tree_extend_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, hipMemcpyKind kind,
+                              void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  MerkleTree* t;
+  Device* d;
+  int rc = tree_enter(handle, &t, &d);
+  if (rc) return rc;
+  if (k == 0) return PV_OK;
+  if (!leaf_hashes) return fail(PV_EINVAL, "null buffer");
+  if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  rc = tree_grow(*t, 0, t->n + k, s);
+  if (rc) return rc;
+  HIP_OK(hipMemcpyAsync(t->lv[0] + 8 * t->n, leaf_hashes, k * 32, kind, s));
+  rc = tree_rebuild(*t, t->n + k, s);
+  if (rc) return rc;
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_tree_extend_hashes_device(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, void* stream) {
+  return tree_extend_hashes(handle, leaf_hashes, k, hipMemcpyDeviceToDevice, stream);
+}
+
+int pv_merkle_tree_extend_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64_t k) {
+  return tree_extend_hashes(handle, leaf_hashes, k, hipMemcpyHostToDevice, nullptr);
+}
+
+int pv_merkle_tree_extend(int32_t handle, const uint8_t* blob, const uint64_t* off, uint64_t k) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  MerkleTree* t;
+  Device* d;
+  int rc = tree_enter(handle, &t, &d);
+  if (rc) return rc;
+  if (k == 0) return PV_OK;
+  if (!off || (!blob && off[k] != off[0])) return fail(PV_EINVAL, "null buffer");
+  if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
+  rc = offsets_ok(off, k, "off");
+  if (rc) return rc;
+  hipStream_t s = d->stream;
+  const uint64_t b0 = off[0], bytes = off[k] - b0;
+  std::vector<uint64_t> offs(k + 1);
+  for (uint64_t i = 0; i <= k; ++i) offs[i] = off[i] - b0;
+  HIP_OK(d->blob.ensure(bytes + 16));
+  HIP_OK(d->off.ensure(k + 1));
+  if (bytes) HIP_OK(hipMemcpyAsync(d->blob.p, blob + b0, bytes, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemsetAsync(d->blob.p + bytes, 0, 16, s));
+  HIP_OK(hipMemcpyAsync(d->off.p, offs.data(), (k + 1) * 8, hipMemcpyHostToDevice, s));
+  rc = tree_grow(*t, 0, t->n + k, s);
+  if (rc) return rc;
+  HIP_OK(pv::launch_sha256(d->blob.p, d->off.p, k, 1, 0x00, d->counter.p, t->lv[0] + 8 * t->n, d->sha256_blocks, s));
+  rc = tree_rebuild(*t, t->n + k, s);
+  if (rc) return rc;
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_tree_info(int32_t handle, uint64_t* n, uint32_t* depth, uint8_t* root) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  MerkleTree* t;
+  Device* d;
+  int rc = tree_enter(handle, &t, &d);
+  if (rc) return rc;
+  if (n) *n = t->n;
+  if (depth) *depth = t->depth;
+  if (root) {
+    if (t->n == 0) {   // hash_empty(): SHA-256 of the empty string (ledger/tree_hasher.py:17-19)
+      static const uint32_t empty[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
+                                        0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
+      memcpy(root, empty, 32);
+    } else {
+      HIP_OK(hipMemcpyAsync(root, t->lv[t->depth], 32, hipMemcpyDeviceToHost, d->stream));
+      HIP_OK(hipStreamSynchronize(d->stream));
+    }
+  }
+  return PV_OK;
+}
+
+// k requests over a resident tree: audit paths (a = index, b = tree_size, roots_out given) or
+// consistency proofs (a = first, b = second).  host: the arrays are host memory and every
+// request is checked before any launch; else they are device memory and the kernel marks a
+// refused request in its length.
+static int tree_requests(int32_t handle, const uint64_t* a, const uint64_t* b, uint64_t k, uint8_t* nodes_out,
+                         uint32_t* len_out, uint8_t* roots_out, bool paths, bool host, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  MerkleTree* t;
+  Device* d;
+  int rc = tree_enter(handle, &t, &d);
+  if (rc) return rc;
+  if (k == 0) return PV_OK;
+  if (!a || !b || !nodes_out || !len_out || (paths && !roots_out)) return fail(PV_EINVAL, "null buffer");
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  const uint64_t node_bytes = k * ((uint64_t)t->depth + 1) * 32;
+  TmpBuf<uint64_t> da, db;
+  TmpBuf<uint8_t> dnodes, droots;
+  TmpBuf<uint32_t> dlen;
+  const uint64_t *pa = a, *pb = b;
+  uint8_t *pn = nodes_out, *pr = roots_out;
+  uint32_t* pl = len_out;
+  if (host) {
+    for (uint64_t i = 0; i < k; ++i)   // refused before any launch, never clamped
+      if (paths ? (b[i] == 0 || b[i] > t->n || a[i] >= b[i]) : (a[i] > b[i] || b[i] > t->n))
+        return fail(PV_EINVAL, "request %llu: (%llu, %llu) outside a tree of %llu leaves", (unsigned long long)i,
+                    (unsigned long long)a[i], (unsigned long long)b[i], (unsigned long long)t->n);
+    HIP_OK(da.put(a, k, s));
+    HIP_OK(db.put(b, k, s));
+    HIP_OK(dnodes.alloc(node_bytes));
+    HIP_OK(droots.alloc(k * 32));
+    HIP_OK(dlen.alloc(k));
+    pa = da.p, pb = db.p, pn = dnodes.p, pr = droots.p, pl = dlen.p;
+  } else if (misaligned16(nodes_out) || misaligned16(roots_out)) {
+    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  }
+  if (paths)
+    HIP_OK(pv::launch_merkle_paths(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, w32(pr), merkle_blocks(*d), s));
+  else
+    HIP_OK(pv::launch_merkle_cons_proofs(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, merkle_blocks(*d), s));
+  if (host) {
+    HIP_OK(hipMemcpyAsync(nodes_out, pn, node_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(len_out, pl, k * 4, hipMemcpyDeviceToHost, s));
+    if (paths) HIP_OK(hipMemcpyAsync(roots_out, pr, k * 32, hipMemcpyDeviceToHost, s));
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_merkle_audit_paths_device(int32_t handle, const uint64_t* index, const uint64_t* tree_size, uint64_t k,
+                                 uint8_t* nodes_out, uint32_t* len_out, uint8_t* roots_out, void* stream) {
+  return tree_requests(handle, index, tree_size, k, nodes_out, len_out, roots_out, true, false, stream);
+}
+
+int pv_merkle_audit_paths(int32_t handle, const uint64_t* index, const uint64_t* tree_size, uint64_t k,
+                          uint8_t* nodes_out, uint32_t* len_out, uint8_t* roots_out) {
+  return tree_requests(handle, index, tree_size, k, nodes_out, len_out, roots_out, true, true, nullptr);
+}
+
+int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t* first, const uint64_t* second, uint64_t k,
+                                        uint8_t* nodes_out, uint32_t* len_out, void* stream) {
+  return tree_requests(handle, first, second, k, nodes_out, len_out, nullptr, false, false, stream);
+}
+
+int pv_merkle_consistency_proofs(int32_t handle, const uint64_t* first, const uint64_t* second, uint64_t k,
+                                 uint8_t* nodes_out, uint32_t* len_out) {
+  return tree_requests(handle, first, second, k, nodes_out, len_out, nullptr, false, true, nullptr);
 }
 
 int pv_synth_layout_device(uint32_t cfg, uint32_t mode, uint64_t first, uint64_t n, uint32_t mlen_min,

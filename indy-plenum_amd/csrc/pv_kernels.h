@@ -156,6 +156,33 @@ hipError_t launch_merkle_level(const uint32_t* in, uint64_t m, uint32_t* out, hi
 constexpr int MERKLE_TAIL = 256;
 hipError_t launch_merkle_tail(const uint32_t* in, uint64_t m, uint32_t* root, hipStream_t s);
 
+// Merkle audit paths / consistency proofs (pv_merkle_proof.h), one proof or
+// request per lane; digests are 8 words each and 16-byte aligned, proof_off
+// (n + 1 entries) counts nodes, max_blocks caps the grid-stride grid.
+//   verify_incl  leaf (n x 8) + index / tree_size + nodes -> status, computed, stop_index;
+//                proof i's root is roots[root_idx ? root_idx[i] : i]
+//   verify_cons  the same for (old_size, new_size) pairs and their two roots
+//   level_keep   parents first_out .. ceil(m/2) - 1 of one level (resident tree)
+//   paths / cons_proofs  lv = device table of level pointers of a tree of n
+//                leaves and `depth` levels above them; request i writes at most
+//                depth + 1 nodes at stride depth + 1, its length (MP_LEN_REFUSED
+//                for a request outside the tree) and, for paths, MTH(0, s)
+hipError_t launch_merkle_verify_incl(const uint32_t* leaf, const uint64_t* index, const uint64_t* tree_size,
+                                     const uint32_t* nodes, const uint64_t* proof_off, const uint32_t* roots,
+                                     const uint32_t* root_idx, uint64_t n, uint8_t* status, uint32_t* computed,
+                                     uint64_t* stop_index, int max_blocks, hipStream_t s);
+hipError_t launch_merkle_verify_cons(const uint64_t* old_size, const uint64_t* new_size, const uint32_t* old_roots,
+                                     const uint32_t* new_roots, const uint32_t* old_idx, const uint32_t* new_idx,
+                                     const uint32_t* nodes, const uint64_t* proof_off, uint64_t n, uint8_t* status,
+                                     uint32_t* old_computed, uint32_t* new_computed, int max_blocks, hipStream_t s);
+hipError_t launch_merkle_level_keep(const uint32_t* in, uint64_t first_out, uint64_t m, uint32_t* out, hipStream_t s);
+hipError_t launch_merkle_paths(const uint32_t* const* lv, uint64_t n, uint32_t depth, const uint64_t* index,
+                               const uint64_t* tree_size, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
+                               uint32_t* roots_out, int max_blocks, hipStream_t s);
+hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint32_t depth, const uint64_t* first,
+                                     const uint64_t* second, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
+                                     int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

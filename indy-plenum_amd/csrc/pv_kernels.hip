@@ -15,7 +15,9 @@
 #include "pv_verify_core.h"
 #include "pv_quad.h"
 #include "pv_sha256.h"
+#include "pv_merkle_proof.h"
 #include "pv_kernels.h"
+#include "plenum_verify.h"
 
 namespace pv {
 
@@ -1477,6 +1479,198 @@ hipError_t launch_merkle_tail(const uint32_t* in, uint64_t m, uint32_t* root, hi
 hipError_t sha256_occupancy(int* blocks_per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void*>(k_sha256), 256,
                                                       0);
+}
+
+// ------------------------------------- Merkle audit paths / consistency proofs
+// One proof per lane, grid-stride by whole blocks so that a wave stays
+// together; pv_merkle_proof.h holds the walks.  Every step of a walk consumes
+// one proof node and hashes once (operands by select), so the lanes of a wave
+// differ in trip count only and the loop runs while any lane walks.
+static_assert(MP_OK == PV_MP_OK && MP_BAD_RANGE == PV_MP_BAD_RANGE && MP_TOO_SHORT == PV_MP_TOO_SHORT &&
+                  MP_TOO_LONG == PV_MP_TOO_LONG && MP_ROOT_MISMATCH == PV_MP_ROOT_MISMATCH &&
+                  MP_INCONSISTENT == PV_MP_INCONSISTENT && MP_LEN_REFUSED == PV_MP_LEN_REFUSED,
+              "public Merkle proof status codes");
+__global__ __launch_bounds__(256) void k_merkle_verify_incl(
+    const uint32_t* __restrict__ leaf, const uint64_t* __restrict__ index, const uint64_t* __restrict__ tree_size,
+    const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ proof_off, const uint32_t* __restrict__ roots,
+    const uint32_t* __restrict__ root_idx, uint64_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ computed,
+    uint64_t* __restrict__ stop_index) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < n; i0 += stride) {
+    const uint64_t i = i0 + threadIdx.x;
+    const bool valid = i < n;
+    MpIncl s;
+    s.phase = MP_FINAL;
+    const uint32_t* pn = nodes;
+    if (valid) {
+      uint32_t lh[8];
+      mp_load(lh, leaf + 8 * i);
+      const uint64_t o = proof_off[i];
+      pn = nodes + 8 * o;
+      mp_incl_begin(s, lh, index[i], tree_size[i], pn, proof_off[i + 1] - o);
+    }
+    while (__any(s.phase == MP_WALK)) {
+      if (s.phase == MP_WALK) mp_incl_step(s, pn);
+    }
+    if (valid) {
+      uint32_t r[8];
+      mp_load(r, roots + 8 * (root_idx ? (uint64_t)root_idx[i] : i));
+      status[i] = (uint8_t)mp_incl_finish(s, r);
+      mp_store(computed + 8 * i, s.h);
+      stop_index[i] = s.stop;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_merkle_verify_cons(
+    const uint64_t* __restrict__ old_size, const uint64_t* __restrict__ new_size,
+    const uint32_t* __restrict__ old_roots, const uint32_t* __restrict__ new_roots,
+    const uint32_t* __restrict__ old_idx, const uint32_t* __restrict__ new_idx, const uint32_t* __restrict__ nodes,
+    const uint64_t* __restrict__ proof_off, uint64_t n, uint8_t* __restrict__ status,
+    uint32_t* __restrict__ old_computed, uint32_t* __restrict__ new_computed) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < n; i0 += stride) {
+    const uint64_t i = i0 + threadIdx.x;
+    const bool valid = i < n;
+    MpCons s;
+    s.phase = MP_FINAL;
+    const uint32_t* pn = nodes;
+    uint64_t ro = 0, rn = 0;
+    if (valid) {
+      ro = old_idx ? (uint64_t)old_idx[i] : i;
+      rn = new_idx ? (uint64_t)new_idx[i] : i;
+      uint32_t r0[8], r1[8];
+      mp_load(r0, old_roots + 8 * ro);
+      mp_load(r1, new_roots + 8 * rn);
+      const uint64_t o = proof_off[i];
+      pn = nodes + 8 * o;
+      mp_cons_begin(s, old_size[i], new_size[i], r0, r1, pn, proof_off[i + 1] - o);
+    }
+    while (__any(s.phase == MP_WALK)) {
+      if (s.phase == MP_WALK) mp_cons_step(s, pn);
+    }
+    if (valid) {
+      uint32_t r0[8], r1[8];   // reloaded: not kept in registers across the walk
+      mp_load(r0, old_roots + 8 * ro);
+      mp_load(r1, new_roots + 8 * rn);
+      status[i] = (uint8_t)mp_cons_finish(s, r0, r1);
+      mp_store(old_computed + 8 * i, s.oh);
+      mp_store(new_computed + 8 * i, s.nh);
+    }
+  }
+}
+
+// k_merkle_level with a start index: parents first_out .. ceil(m/2) - 1 of the
+// m nodes of `in` (the odd last node moves up unchanged).  Builds and extends
+// a resident tree whose levels are kept.
+__global__ __launch_bounds__(256) void k_merkle_level_keep(const uint32_t* __restrict__ in, uint64_t first_out,
+                                                           uint64_t m, uint32_t* __restrict__ out) {
+  const uint64_t i = first_out + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t half = m / 2;
+  if (i < half) {
+    uint32_t lr[16], h[8];
+    mp_load(lr, in + 16 * i);
+    mp_load(lr + 8, in + 16 * i + 8);
+    sha256_node(h, lr);
+    mp_store(out + 8 * i, h);
+  } else if (i == half && (m & 1)) {
+    uint32_t h[8];
+    mp_load(h, in + 8 * (m - 1));
+    mp_store(out + 8 * i, h);
+  }
+}
+
+// One request per lane over the resident levels (lv = device table of level
+// pointers, n leaves, depth levels above them).  Request i writes at most
+// depth + 1 nodes at nodes_out + i * (depth + 1) * 8 words.  A request outside
+// the tree is refused, not clamped: len MP_LEN_REFUSED, nothing else written.
+__global__ __launch_bounds__(256) void k_merkle_paths(const uint32_t* const* __restrict__ lv, uint64_t n,
+                                                      uint32_t depth, const uint64_t* __restrict__ index,
+                                                      const uint64_t* __restrict__ tree_size, uint64_t k,
+                                                      uint32_t* __restrict__ nodes_out, uint32_t* __restrict__ len_out,
+                                                      uint32_t* __restrict__ roots_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < k; i += stride) {
+    const uint64_t m = index[i], s = tree_size[i];
+    if (s == 0 || s > n || m >= s) {
+      len_out[i] = MP_LEN_REFUSED;
+      continue;
+    }
+    uint32_t root[8];
+    len_out[i] = mp_audit_path(lv, n, m, s, nodes_out + i * (uint64_t)(depth + 1) * 8, root);
+    mp_store(roots_out + 8 * i, root);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_merkle_cons_proofs(const uint32_t* const* __restrict__ lv, uint64_t n,
+                                                            uint32_t depth, const uint64_t* __restrict__ first,
+                                                            const uint64_t* __restrict__ second, uint64_t k,
+                                                            uint32_t* __restrict__ nodes_out,
+                                                            uint32_t* __restrict__ len_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < k; i += stride) {
+    const uint64_t a = first[i], b = second[i];
+    if (a > b || b > n) {
+      len_out[i] = MP_LEN_REFUSED;
+      continue;
+    }
+    len_out[i] = mp_cons_proof(lv, n, a, b, nodes_out + i * (uint64_t)(depth + 1) * 8);
+  }
+}
+
+namespace {
+uint32_t mp_grid(uint64_t items, int max_blocks) {
+  const uint64_t need = (items + 255) / 256;
+  const uint64_t cap = max_blocks < 1 ? 1 : (uint64_t)max_blocks;
+  return (uint32_t)(need < cap ? need : cap);
+}
+}  // namespace
+
+hipError_t launch_merkle_verify_incl(const uint32_t* leaf, const uint64_t* index, const uint64_t* tree_size,
+                                     const uint32_t* nodes, const uint64_t* proof_off, const uint32_t* roots,
+                                     const uint32_t* root_idx, uint64_t n, uint8_t* status, uint32_t* computed,
+                                     uint64_t* stop_index, int max_blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_verify_incl, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, leaf, index, tree_size,
+                     nodes, proof_off, roots, root_idx, n, status, computed, stop_index);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_verify_cons(const uint64_t* old_size, const uint64_t* new_size, const uint32_t* old_roots,
+                                     const uint32_t* new_roots, const uint32_t* old_idx, const uint32_t* new_idx,
+                                     const uint32_t* nodes, const uint64_t* proof_off, uint64_t n, uint8_t* status,
+                                     uint32_t* old_computed, uint32_t* new_computed, int max_blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_verify_cons, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, old_size, new_size,
+                     old_roots, new_roots, old_idx, new_idx, nodes, proof_off, n, status, old_computed, new_computed);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_level_keep(const uint32_t* in, uint64_t first_out, uint64_t m, uint32_t* out, hipStream_t s) {
+  const uint64_t outs = (m + 1) / 2;
+  if (first_out >= outs) return hipSuccess;
+  const uint64_t blocks = (outs - first_out + 255) / 256;
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_merkle_level_keep, dim3((uint32_t)blocks), dim3(256), 0, s, in, first_out, m, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_paths(const uint32_t* const* lv, uint64_t n, uint32_t depth, const uint64_t* index,
+                               const uint64_t* tree_size, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
+                               uint32_t* roots_out, int max_blocks, hipStream_t s) {
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_paths, dim3(mp_grid(k, max_blocks)), dim3(256), 0, s, lv, n, depth, index, tree_size, k,
+                     nodes_out, len_out, roots_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint32_t depth, const uint64_t* first,
+                                     const uint64_t* second, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
+                                     int max_blocks, hipStream_t s) {
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_cons_proofs, dim3(mp_grid(k, max_blocks)), dim3(256), 0, s, lv, n, depth, first, second,
+                     k, nodes_out, len_out);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------- synthetic workload

@@ -14,9 +14,23 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
   req_authenticator  ReqAuthenticator (+ verify_batch)       plenum/server/req_authenticator.py
   quorums, models Quorums / Commits / Prepares (+ tally_batches)
                   plenum/server/quorums.py, plenum/server/models.py
+  merkle          GpuTreeHasher, sha256_batch, merkle_root      ledger/tree_hasher.py
+  merkle_proofs   GpuMerkleVerifier (+ *_batch), GpuMerkleTree
+                  ledger/merkle_verifier.py, ledger/compact_merkle_tree.py
   serialization, base58, exceptions, constants   the data formats either side
 
 device.py holds the device-resident (torch tensor) entry points; _native.py is
 the ctypes binding.  Nothing here verifies on the CPU.
 """
 __version__ = '0.1.0'
+
+# exported from merkle_proofs, imported on first use (the package import stays light)
+_MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
+__all__ = list(_MERKLE_PROOFS)
+
+
+def __getattr__(name):
+    if name in _MERKLE_PROOFS:
+        from . import merkle_proofs
+        return getattr(merkle_proofs, name)
+    raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -69,6 +69,27 @@ SIGNATURES = [
     ('pv_sha256_batch_device', ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int32, _vp, ctypes.c_int, _vp]),
     ('pv_merkle_root', ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_merkle_root_device', ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_int, _vp]),
+    ('pv_merkle_verify_inclusion', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp]),
+    ('pv_merkle_verify_inclusion_device', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_int,
+      _vp]),
+    ('pv_merkle_verify_consistency', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    ('pv_merkle_verify_consistency_device', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    ('pv_merkle_tree_create', ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    ('pv_merkle_tree_extend', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64]),
+    ('pv_merkle_tree_extend_hashes', ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_uint64]),
+    ('pv_merkle_tree_extend_hashes_device', ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_uint64, _vp]),
+    ('pv_merkle_tree_info', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), _vp]),
+    ('pv_merkle_tree_free', ctypes.c_int, [ctypes.c_int32]),
+    ('pv_merkle_audit_paths', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    ('pv_merkle_audit_paths_device', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    ('pv_merkle_consistency_proofs', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    ('pv_merkle_consistency_proofs_device', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
     ('pv_verify_keyed_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_int, _vp]),
     ('pv_time_verify_keyed_device', ctypes.c_int,

@@ -123,3 +123,21 @@ class NoAuthenticatorFound(SigningException):
 class InvalidKey(Exception):
     code = 142
     reason = 'invalid key'
+
+
+# Error contract of the Merkle proof path (merkle_proofs.py): the hierarchy of
+# ledger/error.py:44-70, caught by class.
+class Error(Exception):
+    """Exceptions raised by the crypto subpackage."""
+
+
+class VerifyError(Error):
+    """Some expected property of the input cannot be verified."""
+
+
+class ConsistencyError(VerifyError):
+    """There is a (cryptographic) inconsistency in the data."""
+
+
+class ProofError(VerifyError):
+    """A cryptographic proof is not valid."""
