@@ -323,6 +323,63 @@ int pv_merkle_consistency_proofs(int32_t handle, const uint64_t *first, const ui
 int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t *first, const uint64_t *second, uint64_t k,
                                         uint8_t *nodes_out, uint32_t *len_out, void *stream);
 
+/* SHA3-256 and Patricia-trie state proofs, batched: the third check of a read reply
+ * (plenum/server/request_handlers/handler_interfaces/read_request_handler.py:39-59).
+ *   pv_sha3_256_batch[_device]
+ *       digests[i] (32 bytes) = SHA3-256(M_i), M_i = blob[off[i] .. off[i+1]): the trie's
+ *       hashlib.sha3_256 (state/util/utils.py:7-8,156-157).
+ *   pv_rlp_split_list   (host only, no GPU)
+ *       The top-level items of the RLP list rlp[0 .. len), in place: item k is
+ *       rlp[item_beg[k] .. item_end[k]) with its own header.  This is how the nodes of a
+ *       serialized proof (Trie.serialize_proof = rlp(list of nodes),
+ *       state/trie/pruning_trie.py:1164-1170) are found without copying them.  *count = the
+ *       number of items.  PV_EINVAL when the input is not one list whose items end exactly at
+ *       its end, or when it holds more than cap items.  Lengths decode as in
+ *       state/util/fast_rlp.py:47-71 (lenient), every one checked against the enclosing end.
+ *   pv_state_proof_verify[_device]
+ *       Trie.verify_spv_proof / verify_spv_proof_multi (pruning_trie.py:1100-1162; what
+ *       PruningState.verify_state_proof[_multi], state/pruning_state.py:113-128, call after
+ *       encode_kv_for_verification) for Q queries over P proofs.  The N nodes of all proofs are
+ *       byte ranges node_blob[node_beg[j] .. node_end[j]), each one RLP list; proof p owns nodes
+ *       proof_first[p] .. proof_first[p+1] - 1 (P + 1 entries, monotone, the last == N) and is
+ *       trusted up to roots[p] (32 bytes).  Query i checks that proof proof_idx[i] ties key i
+ *       (key_blob / key_off) to the ENCODED value i (val_blob / val_off; empty = None = absent).
+ *       Every node is hashed once (k_sha3_256), however many queries name its proof; then one
+ *       lane per query walks the trie.  status[i] is one of PV_SP_*; the reference's verdict is
+ *       status[i] == PV_SP_OK (for _multi: all of its queries).
+ *       Host form: PV_EINVAL before any launch (status untouched) for non-monotone key_off /
+ *       val_off, node_beg[j] > node_end[j] or node_end[j] > node_blob_len, a proof_first that is
+ *       not monotone or does not end at N, or proof_idx[i] >= P.  Q == 0 launches nothing.
+ *       Device form: DEVICE buffers, not checked; node_blob 4-byte aligned with >= 16 readable
+ *       bytes after the last node; roots 4-byte aligned; node_digests (N x 32, 16-byte
+ *       aligned) receives the node digests.
+ * pv_sha3_256_batch_device: DEVICE buffers; blob 4-byte aligned (checked) with >= 16 readable
+ * bytes after the last message (a lane loads whole aligned 16-byte groups); digests 16-byte
+ * aligned (checked).
+ * Two deliberate differences from the reference: a node that is not well-formed RLP of a trie
+ * node (reachable from a trusted root only through a SHA3 preimage) gives PV_SP_MALFORMED by
+ * rule, never an out-of-bounds read, whatever exception pyrlp would raise; and splitting a
+ * serialized proof is the caller's step, so an undecodable one is the caller's False. */
+#define PV_SP_OK 0
+#define PV_SP_VALUE_MISMATCH 1 /* the trie holds another value, or none, for the key */
+#define PV_SP_NODE_MISSING 2   /* the root or a referenced node is not among the proof's nodes */
+#define PV_SP_MALFORMED 3      /* a node on the path is not a well-formed trie node */
+int pv_sha3_256_batch(const uint8_t *blob, const uint64_t *off, uint64_t n, uint8_t *digests);
+int pv_sha3_256_batch_device(const uint8_t *blob, const uint64_t *off, uint64_t n, uint8_t *digests, int device,
+                             void *stream);
+int pv_rlp_split_list(const uint8_t *rlp, uint64_t len, uint64_t *item_beg, uint64_t *item_end, uint64_t cap,
+                      uint64_t *count);
+int pv_state_proof_verify(const uint8_t *node_blob, uint64_t node_blob_len, const uint64_t *node_beg,
+                          const uint64_t *node_end, const uint64_t *proof_first, const uint8_t *roots,
+                          const uint32_t *proof_idx, const uint8_t *key_blob, const uint64_t *key_off,
+                          const uint8_t *val_blob, const uint64_t *val_off, uint64_t N, uint64_t P, uint64_t Q,
+                          uint8_t *status);
+int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_beg, const uint64_t *node_end,
+                                 const uint64_t *proof_first, const uint8_t *roots, const uint32_t *proof_idx,
+                                 const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob,
+                                 const uint64_t *val_off, uint64_t N, uint64_t P, uint64_t Q, uint8_t *status,
+                                 uint8_t *node_digests, int device, void *stream);
+
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of
  *                 batch b = node 32 w + j cast a valid vote in batch b (a voter SET:

@@ -25,7 +25,11 @@
 
 #include "../../include/plenum_verify.h"
 #include "pv_kernels.h"
+#include "pv_trie_proof.h"
 
+static_assert(pv::SP_OK == PV_SP_OK && pv::SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
+                  pv::SP_NODE_MISSING == PV_SP_NODE_MISSING && pv::SP_MALFORMED == PV_SP_MALFORMED,
+              "public state-proof status codes");
 static_assert(PV_KEY_WORDS == (unsigned)pv::KEYTAB_WORDS, "prepared-key layout");
 static_assert(PV_KEY_WORDS_WIDE == (unsigned)pv::KEYTAB_WIDE_WORDS, "wide prepared-key layout");
 
@@ -479,6 +483,7 @@ struct Device {
   uint64_t kc_count = 0;        // slots prepared on this device
   DevBuf<uint8_t> kcpk;         // staging of keys being added
   int sha256_blocks = 0;
+  int sha3_blocks = 0;
   int curve_blocks_keyed = 0;
   int curve_half_blocks = 0;
   CurveMode mode = CurveMode::Half;
@@ -641,6 +646,9 @@ int init_device(Device& d) {
   int sper = 0;
   HIP_OK(pv::sha256_occupancy(&sper));
   d.sha256_blocks = d.cu_count * (sper < 1 ? 1 : sper);
+  int kper3 = 0;
+  HIP_OK(pv::sha3_occupancy(&kper3));
+  d.sha3_blocks = d.cu_count * (kper3 < 1 ? 1 : kper3);
   int hper = 0;
   HIP_OK(pv::hash_occupancy(&hper));
   if (hper < 1) hper = 1;
@@ -2708,6 +2716,151 @@ int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t* first, c
 int pv_merkle_consistency_proofs(int32_t handle, const uint64_t* first, const uint64_t* second, uint64_t k,
                                  uint8_t* nodes_out, uint32_t* len_out) {
   return tree_requests(handle, first, second, k, nodes_out, len_out, nullptr, false, true, nullptr);
+}
+
+// ------------------------------------------------ SHA3-256 / state proofs
+int pv_sha3_256_batch_device(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* digests, int device,
+                             void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  Device* d = find_dev(device);
+  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (n == 0) return PV_OK;
+  if (!blob || !off || !digests) return fail(PV_EINVAL, "null device buffer");
+  if (misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(blob) & 3u) return fail(PV_EINVAL, "blob must be 4-byte aligned");
+  HIP_OK(hipSetDevice(d->ord));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  HIP_OK(pv::launch_sha3_256(blob, off, off + 1, n, d->counter.p, w32(digests), d->sha3_blocks, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_sha3_256_batch(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* digests) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  if (n == 0) return PV_OK;
+  if (!off || !digests || (!blob && off[n] != off[0])) return fail(PV_EINVAL, "null buffer");
+  int rc = offsets_ok(off, n, "off");
+  if (rc) return rc;
+  Device& d = g_devs[0];
+  HIP_OK(hipSetDevice(d.ord));
+  const uint64_t b0 = off[0], bytes = off[n] - b0;
+  std::vector<uint64_t> offs(n + 1);
+  for (uint64_t k = 0; k <= n; ++k) offs[k] = off[k] - b0;
+  HIP_OK(d.blob.ensure(bytes + 16));
+  HIP_OK(d.off.ensure(n + 1));
+  HIP_OK(d.mk0.ensure(n * 8));
+  if (bytes) HIP_OK(hipMemcpyAsync(d.blob.p, blob + b0, bytes, hipMemcpyHostToDevice, d.stream));
+  HIP_OK(hipMemsetAsync(d.blob.p + bytes, 0, 16, d.stream));
+  HIP_OK(hipMemcpyAsync(d.off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, d.stream));
+  HIP_OK(pv::launch_sha3_256(d.blob.p, d.off.p, d.off.p + 1, n, d.counter.p, d.mk0.p, d.sha3_blocks, d.stream));
+  HIP_OK(hipMemcpyAsync(digests, d.mk0.p, n * 32, hipMemcpyDeviceToHost, d.stream));
+  HIP_OK(hipStreamSynchronize(d.stream));
+  return PV_OK;
+}
+
+int pv_rlp_split_list(const uint8_t* rlp, uint64_t len, uint64_t* item_beg, uint64_t* item_end, uint64_t cap,
+                      uint64_t* count) {
+  if (!count || (len && !rlp) || (cap && (!item_beg || !item_end))) return fail(PV_EINVAL, "null buffer");
+  if (!pv::rlp_split_list(rlp, len, item_beg, item_end, cap, count))
+    return fail(PV_EINVAL, "not one RLP list of at most %llu items ending at its end", (unsigned long long)cap);
+  return PV_OK;
+}
+
+int pv_state_proof_verify_device(const uint8_t* node_blob, const uint64_t* node_beg, const uint64_t* node_end,
+                                 const uint64_t* proof_first, const uint8_t* roots, const uint32_t* proof_idx,
+                                 const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
+                                 const uint64_t* val_off, uint64_t N, uint64_t P, uint64_t Q, uint8_t* status,
+                                 uint8_t* node_digests, int device, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  Device* d = find_dev(device);
+  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (Q == 0) return PV_OK;
+  if (!proof_first || !roots || !proof_idx || !key_off || !val_off || !status ||
+      (N && (!node_blob || !node_beg || !node_end || !node_digests)))
+    return fail(PV_EINVAL, "null device buffer");
+  if (P == 0) return fail(PV_EINVAL, "queries without proofs");
+  if (misaligned16(node_digests) || (reinterpret_cast<uintptr_t>(roots) & 3u) ||
+      (reinterpret_cast<uintptr_t>(node_blob) & 3u))
+    return fail(PV_EINVAL, "node_digests must be 16-byte aligned, roots and node_blob 4-byte aligned");
+  HIP_OK(hipSetDevice(d->ord));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  HIP_OK(pv::launch_sha3_256(node_blob, node_beg, node_end, N, d->counter.p, w32(node_digests), d->sha3_blocks, s));
+  HIP_OK(pv::launch_trie_verify(node_blob, node_beg, node_end, w32(node_digests), proof_first, w32(roots), P,
+                                proof_idx, key_blob, key_off, val_blob, val_off, Q, status, merkle_blocks(*d), s));
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+int pv_state_proof_verify(const uint8_t* node_blob, uint64_t node_blob_len, const uint64_t* node_beg,
+                          const uint64_t* node_end, const uint64_t* proof_first, const uint8_t* roots,
+                          const uint32_t* proof_idx, const uint8_t* key_blob, const uint64_t* key_off,
+                          const uint8_t* val_blob, const uint64_t* val_off, uint64_t N, uint64_t P, uint64_t Q,
+                          uint8_t* status) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  if (Q == 0) return PV_OK;
+  if (!proof_first || !roots || !proof_idx || !key_off || !val_off || !status ||
+      (N && (!node_beg || !node_end)) || (node_blob_len && !node_blob))
+    return fail(PV_EINVAL, "null buffer");
+  if (P == 0) return fail(PV_EINVAL, "queries without proofs");
+  int rc = offsets_ok(key_off, Q, "key_off");
+  if (rc) return rc;
+  rc = offsets_ok(val_off, Q, "val_off");
+  if (rc) return rc;
+  const uint64_t k0 = key_off[0], kbytes = key_off[Q] - k0, v0 = val_off[0], vbytes = val_off[Q] - v0;
+  if ((kbytes && !key_blob) || (vbytes && !val_blob)) return fail(PV_EINVAL, "null buffer");
+  for (uint64_t j = 0; j < N; ++j)
+    if (node_beg[j] > node_end[j] || node_end[j] > node_blob_len)
+      return fail(PV_EINVAL, "node %llu lies outside the blob", (unsigned long long)j);
+  rc = offsets_ok(proof_first, P, "proof_first");
+  if (rc) return rc;
+  if (proof_first[P] != N)
+    return fail(PV_EINVAL, "proof_first ends at %llu, not at N = %llu", (unsigned long long)proof_first[P],
+                (unsigned long long)N);
+  for (uint64_t i = 0; i < Q; ++i)
+    if (proof_idx[i] >= P)
+      return fail(PV_EINVAL, "proof_idx[%llu] = %u is not below P = %llu", (unsigned long long)i, proof_idx[i],
+                  (unsigned long long)P);
+  Device& d = g_devs[0];
+  HIP_OK(hipSetDevice(d.ord));
+  hipStream_t s = d.stream;
+  std::vector<uint64_t> koff(Q + 1), voff(Q + 1);
+  for (uint64_t i = 0; i <= Q; ++i) {
+    koff[i] = key_off[i] - k0;
+    voff[i] = val_off[i] - v0;
+  }
+  TmpBuf<uint8_t> dblob, droots, dkeys, dvals, dstatus, ddig;
+  TmpBuf<uint64_t> dbeg, dend, dfirst, dkoff, dvoff;
+  TmpBuf<uint32_t> dpidx;
+  HIP_OK(dblob.alloc(node_blob_len + 16));
+  if (node_blob_len) HIP_OK(hipMemcpyAsync(dblob.p, node_blob, node_blob_len, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemsetAsync(dblob.p + node_blob_len, 0, 16, s));
+  HIP_OK(dbeg.put(node_beg, N, s));
+  HIP_OK(dend.put(node_end, N, s));
+  HIP_OK(dfirst.put(proof_first, P + 1, s));
+  HIP_OK(droots.put(roots, P * 32, s));
+  HIP_OK(dpidx.put(proof_idx, Q, s));
+  HIP_OK(dkeys.put(kbytes ? key_blob + k0 : nullptr, kbytes, s));
+  HIP_OK(dkoff.put(koff.data(), Q + 1, s));
+  HIP_OK(dvals.put(vbytes ? val_blob + v0 : nullptr, vbytes, s));
+  HIP_OK(dvoff.put(voff.data(), Q + 1, s));
+  HIP_OK(dstatus.alloc(Q));
+  HIP_OK(ddig.alloc(N * 32));
+  hipError_t e = pv::launch_sha3_256(dblob.p, dbeg.p, dend.p, N, d.counter.p, w32(ddig.p), d.sha3_blocks, s);
+  if (e == hipSuccess)
+    e = pv::launch_trie_verify(dblob.p, dbeg.p, dend.p, w32(ddig.p), dfirst.p, w32(droots.p), P, dpidx.p, dkeys.p,
+                               dkoff.p, dvals.p, dvoff.p, Q, dstatus.p, merkle_blocks(d), s);
+  if (e == hipSuccess) e = hipMemcpyAsync(status, dstatus.p, Q, hipMemcpyDeviceToHost, s);
+  // the call-scoped buffers must outlive the work queued on s
+  const hipError_t e2 = hipStreamSynchronize(s);
+  HIP_OK(e);
+  HIP_OK(e2);
+  return PV_OK;
 }
 
 int pv_synth_layout_device(uint32_t cfg, uint32_t mode, uint64_t first, uint64_t n, uint32_t mlen_min,

@@ -183,6 +183,22 @@ hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint
                                      const uint64_t* second, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
                                      int max_blocks, hipStream_t s);
 
+// SHA3-256 / Patricia-trie state proofs (pv_sha3.h, pv_trie_proof.h).
+//   sha3_256     out (n x 8 words, 16-byte aligned) = SHA3-256(blob[beg[i] .. end[i])); the
+//                work queue of launch_sha256 (`counter` reset by the launch); the blob needs
+//                >= 16 readable bytes after the last message
+//   trie_verify  one query per lane: proof proof_idx[i] = nodes proof_first[p] ..
+//                proof_first[p + 1] - 1 with digests node_dig, root roots[p] (8 words), key and
+//                expected encoded value -> status[i] (SP_*)
+hipError_t sha3_occupancy(int* blocks_per_cu);
+hipError_t launch_sha3_256(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, uint64_t n,
+                           unsigned long long* counter, uint32_t* out, int blocks, hipStream_t s);
+hipError_t launch_trie_verify(const uint8_t* node_blob, const uint64_t* node_beg, const uint64_t* node_end,
+                              const uint32_t* node_dig, const uint64_t* proof_first, const uint32_t* roots,
+                              uint64_t n_proofs, const uint32_t* proof_idx, const uint8_t* key_blob,
+                              const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off, uint64_t n,
+                              uint8_t* status, int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

@@ -16,6 +16,8 @@
 #include "pv_quad.h"
 #include "pv_sha256.h"
 #include "pv_merkle_proof.h"
+#include "pv_sha3.h"
+#include "pv_trie_proof.h"
 #include "pv_kernels.h"
 #include "plenum_verify.h"
 
@@ -1670,6 +1672,120 @@ hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint
   if (k == 0) return hipSuccess;
   hipLaunchKernelGGL(k_merkle_cons_proofs, dim3(mp_grid(k, max_blocks)), dim3(256), 0, s, lv, n, depth, first, second,
                      k, nodes_out, len_out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------- SHA3-256 / state-proof verification
+// Batch SHA3-256 of the byte ranges blob[beg[i] .. end[i]): one message per
+// lane, ragged, on k_sha256's persistent-lane work queue (one Keccak
+// permutation per trip; a 33-byte node and a 600-byte node in one wave differ
+// in trip count only).  The next trip's window is loaded during the current
+// permutation.  out (n x 8 words) must be 16-byte aligned: each digest leaves
+// as two 16-byte stores.
+__global__ __launch_bounds__(256) void k_sha3_256(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ beg,
+                                                   const uint64_t* __restrict__ end, uint64_t n,
+                                                   unsigned long long* __restrict__ counter,
+                                                   uint32_t* __restrict__ out) {
+  WaveQueue q;
+  wq_init<false>(q, counter, n, 64);
+  uint64_t idx = n, blk = 0, nblk = 0, mo = 0, ml = 0;
+  uint64_t nidx = wq_take<false>(q, true, counter), nmo = 0, nme = 0;
+  if (nidx < n) {
+    nmo = beg[nidx];
+    nme = end[nidx];
+  }
+  Sha3State st;
+  sha3_init(st);
+  uint32_t y[SHA3_Y];   // the window of the block this lane absorbs next
+  if (nidx < n) sha3_window(y, blob + nmo, nme - nmo, 0);
+  while (true) {
+    const bool promote = blk == nblk && nidx < n;
+    if (promote) {
+      idx = nidx;
+      mo = nmo;
+      ml = nme - nmo;
+      nblk = sha3_blocks(ml);
+      blk = 0;
+      sha3_init(st);
+    }
+    const uint64_t t = wq_take<false>(q, promote, counter);
+    if (promote) {
+      nidx = t;
+      if (nidx < n) {
+        nmo = beg[nidx];
+        nme = end[nidx];
+      }
+    }
+    const bool active = blk < nblk;
+    if (!__any(active)) break;   // every message promotes on the trip it is taken
+    if (active) {
+      uint32_t w[SHA3_RATE_WORDS];
+      sha3_assemble(w, y, blob + mo, ml, blk);
+      if (blk + 1 < nblk) sha3_window(y, blob + mo, ml, blk + 1);
+      else if (nidx < n) sha3_window(y, blob + nmo, nme - nmo, 0);
+      sha3_absorb(st, w);
+      if (++blk == nblk) {
+        uint4* o = reinterpret_cast<uint4*>(out + 8 * idx);
+        o[0] = make_uint4(st.l0, st.h0, st.l1, st.h1);
+        o[1] = make_uint4(st.l2, st.h2, st.l3, st.h3);
+      }
+    }
+  }
+}
+
+hipError_t launch_sha3_256(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, uint64_t n,
+                           unsigned long long* counter, uint32_t* out, int blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(counter, 0, sizeof(unsigned long long), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sha3_256, dim3(mp_grid(n, blocks)), dim3(256), 0, s, blob, beg, end, n, counter, out);
+  return hipGetLastError();
+}
+
+hipError_t sha3_occupancy(int* blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void*>(k_sha3_256), 256,
+                                                      0);
+}
+
+// One state-proof query per lane (pv_trie_proof.h): query i names proof
+// proof_idx[i] (nodes proof_first[p] .. proof_first[p + 1] - 1, their digests
+// from k_sha3_256), a key and the expected encoded value.  Many queries may
+// name one proof; its nodes were hashed once.
+static_assert(SP_OK == PV_SP_OK && SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
+                  SP_NODE_MISSING == PV_SP_NODE_MISSING && SP_MALFORMED == PV_SP_MALFORMED,
+              "public state-proof status codes");
+__global__ __launch_bounds__(256) void k_trie_verify(
+    const uint8_t* __restrict__ node_blob, const uint64_t* __restrict__ node_beg,
+    const uint64_t* __restrict__ node_end, const uint32_t* __restrict__ node_dig,
+    const uint64_t* __restrict__ proof_first, const uint32_t* __restrict__ roots, uint64_t n_proofs,
+    const uint32_t* __restrict__ proof_idx, const uint8_t* __restrict__ key_blob,
+    const uint64_t* __restrict__ key_off, const uint8_t* __restrict__ val_blob, const uint64_t* __restrict__ val_off,
+    uint64_t n, uint8_t* __restrict__ status) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const uint64_t p = proof_idx[i];
+    uint32_t st = SP_MALFORMED;
+    if (p < n_proofs) {
+      uint32_t r[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[k] = roots[8 * p + k];
+      const uint64_t ko = key_off[i], vo = val_off[i];
+      st = sp_verify(node_blob, node_beg, node_end, node_dig, proof_first[p], proof_first[p + 1], r, key_blob + ko,
+                     key_off[i + 1] - ko, val_blob + vo, val_off[i + 1] - vo);
+    }
+    status[i] = (uint8_t)st;
+  }
+}
+
+hipError_t launch_trie_verify(const uint8_t* node_blob, const uint64_t* node_beg, const uint64_t* node_end,
+                              const uint32_t* node_dig, const uint64_t* proof_first, const uint32_t* roots,
+                              uint64_t n_proofs, const uint32_t* proof_idx, const uint8_t* key_blob,
+                              const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off, uint64_t n,
+                              uint8_t* status, int max_blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_verify, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, node_blob, node_beg, node_end,
+                     node_dig, proof_first, roots, n_proofs, proof_idx, key_blob, key_off, val_blob, val_off, n,
+                     status);
   return hipGetLastError();
 }
 

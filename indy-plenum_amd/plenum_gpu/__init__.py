@@ -17,6 +17,8 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
   merkle          GpuTreeHasher, sha256_batch, merkle_root      ledger/tree_hasher.py
   merkle_proofs   GpuMerkleVerifier (+ *_batch), GpuMerkleTree
                   ledger/merkle_verifier.py, ledger/compact_merkle_tree.py
+  state_proofs    GpuStateVerifier (+ verify_state_proofs_batch), sha3_256_batch
+                  state/pruning_state.py, state/trie/pruning_trie.py
   serialization, base58, exceptions, constants   the data formats either side
 
 device.py holds the device-resident (torch tensor) entry points; _native.py is
@@ -26,11 +28,15 @@ __version__ = '0.1.0'
 
 # exported from merkle_proofs, imported on first use (the package import stays light)
 _MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
-__all__ = list(_MERKLE_PROOFS)
+_STATE_PROOFS = ('GpuStateVerifier', 'verify_state_proofs_batch', 'sha3_256_batch')
+__all__ = list(_MERKLE_PROOFS + _STATE_PROOFS)
 
 
 def __getattr__(name):
     if name in _MERKLE_PROOFS:
         from . import merkle_proofs
         return getattr(merkle_proofs, name)
+    if name in _STATE_PROOFS:
+        from . import state_proofs
+        return getattr(state_proofs, name)
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -90,6 +90,16 @@ SIGNATURES = [
     ('pv_merkle_consistency_proofs', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_merkle_consistency_proofs_device', ctypes.c_int,
      [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    ('pv_sha3_256_batch', ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp]),
+    ('pv_sha3_256_batch_device', ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_int, _vp]),
+    ('pv_rlp_split_list', ctypes.c_int,
+     [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ('pv_state_proof_verify', ctypes.c_int,
+     [_vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+      ctypes.c_uint64, _vp]),
+    ('pv_state_proof_verify_device', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
+      ctypes.c_int, _vp]),
     ('pv_verify_keyed_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_int, _vp]),
     ('pv_time_verify_keyed_device', ctypes.c_int,
