@@ -416,6 +416,36 @@ int ws_end(Workspace& w, hipStream_t s) {
   return PV_OK;
 }
 
+// One use of workspace w on stream s: ordered after the previous use on
+// construction (`rc`), recorded as the last use by end().  An early (error)
+// return records it from the destructor, so later users of the workspace still
+// wait for whatever was queued; after fork(), stream s first waits for the
+// side stream (its tail recorded in `join`), whose work uses the workspace too.
+struct WsUse {
+  Workspace& w;
+  hipStream_t s;
+  const int rc;
+  bool open;
+  hipStream_t side = nullptr;
+  hipEvent_t join = nullptr;
+  WsUse(Workspace& w_, hipStream_t s_) : w(w_), s(s_), rc(ws_begin(w_, s_)), open(rc == PV_OK) {}
+  WsUse(const WsUse&) = delete;
+  WsUse& operator=(const WsUse&) = delete;
+  void fork(hipStream_t side_, hipEvent_t join_) {
+    side = side_;
+    join = join_;
+  }
+  int end() {
+    open = false;
+    return ws_end(w, s);
+  }
+  ~WsUse() {   // no fail() here: the first error stays in pv_last_error()
+    if (!open) return;
+    if (join && hipEventRecord(join, side) == hipSuccess) (void)hipStreamWaitEvent(s, join, 0);
+    if (hipEventRecord(w.done, s) == hipSuccess) w.done_on = s;
+  }
+};
+
 struct Device {
   int id = -1;   // engine device id: the device_mask bit and the `device` argument
   int ord = -1;  // HIP ordinal (== id, except under pv_test_init_dup)
@@ -521,6 +551,40 @@ Device* find_dev(int id) {
     if (d.id == id) return &d;
   return nullptr;
 }
+
+// Scope of one entry point: holds the library lock, restores the caller's
+// current HIP device on exit and resolves the engine device -- `device` (and
+// the workspace slot) of a device-pointer form, device 0 of a host-buffer form.
+// check() is the refusal every form starts with; begin() makes the device
+// current and picks the stream; finish() is the tail of a synchronous form.
+struct Entry {
+  std::lock_guard<std::mutex> lk{g_mu};
+  DeviceGuard dg;
+  const bool host;
+  const int id, slot;
+  Device* d;
+  hipStream_t s = nullptr;
+  explicit Entry(int device, int slot_ = 0) : host(false), id(device), slot(slot_), d(find_dev(device)) {}
+  Entry() : host(true), id(0), slot(0), d(g_devs.empty() ? nullptr : &g_devs[0]) {}
+  int check() const {
+    if (!d)
+      return host ? fail(PV_ENOTINIT, "pv_init has not been called")
+                  : fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", id);
+    if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
+    return PV_OK;
+  }
+  // the caller's stream, else the slot's (slot 0: the device stream)
+  int begin(void* stream = nullptr) {
+    HIP_OK(hipSetDevice(d->ord));
+    s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
+    return PV_OK;
+  }
+  int finish(int rc = PV_OK) {
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize(s));
+    return PV_OK;
+  }
+};
 
 // the process's schedule tuning (include/plenum_verify.h, pv_set_tuning):
 // defaults only, never the environment
@@ -844,8 +908,9 @@ int enqueue_verify(Device& d, Workspace& w, const uint8_t* pk, const uint8_t* si
     lev = d.live_pool[d.live_used++].e;
     ++d.live_launches;
   }
-  int rc = ws_begin(w, s);
-  if (rc) return rc;
+  WsUse use(w, s);
+  if (use.rc) return use.rc;
+  int rc = PV_OK;
   uint64_t* bm = stage_bitmap(w, bitmap, n, rc);
   if (rc) return rc;
   if (timed) HIP_OK(hipEventRecord(d.ev[0], s));
@@ -860,7 +925,7 @@ int enqueue_verify(Device& d, Workspace& w, const uint8_t* pk, const uint8_t* si
   if (curve_after) HIP_OK(hipStreamWaitEvent(s, curve_after, 0));
   rc = enqueue_curve(d, w, pk, sig, blob, off, n, verdict, bm, s, ktab, kidx, wide);
   if (rc) return rc;
-  rc = ws_end(w, s);
+  rc = use.end();
   if (rc) return rc;
   if (lev) HIP_OK(hipEventRecord(lev[2], s));
   if (timed) {
@@ -1037,8 +1102,8 @@ int run_small(Device& d, const HostBatch& hb, uint64_t s, uint64_t e) {
   if (nk) {
     const size_t total_ext = o_ext + 8 + 8 * m;
     if (!zc) HIP_OK(hipMemcpyAsync(d.stage.p, base, total_ext, hipMemcpyHostToDevice, w.stream));
-    int rc = ws_begin(w, w.stream);
-    if (rc) return rc;
+    WsUse use(w, w.stream);
+    if (use.rc) return use.rc;
     const uint64_t* goff = reinterpret_cast<const uint64_t*>(g);
     const uint32_t* kidx = reinterpret_cast<const uint32_t*>(g + o_ext + 8);
     // up to 16 blocks: measured 2-3 us faster than a k_signal launch; at 125
@@ -1058,8 +1123,7 @@ int run_small(Device& d, const HostBatch& hb, uint64_t s, uint64_t e) {
       HIP_OK(pv::launch_verify_quad_list(g + o_pk, g + o_sig, g + o_blob, goff, kidx + 2 * m - ng,
                                          reinterpret_cast<const unsigned long long*>(g + o_ext), ng, (int)((ng + 7) / 8),
                                          d.bw.p, vdst, d.mode == CurveMode::Full, w.stream));
-    rc = ws_end(w, w.stream);
-    if (rc) return rc;
+    if (const int rc = use.end()) return rc;
   } else {
     if (!zc) HIP_OK(hipMemcpyAsync(d.stage.p, base, total, hipMemcpyHostToDevice, w.stream));
     const int rc = enqueue_verify(d, w, g + o_pk, g + o_sig, g + o_blob, reinterpret_cast<const uint64_t*>(g), m,
@@ -1332,6 +1396,30 @@ int run_shard(Device& d, const HostBatch& hb, uint64_t s, uint64_t e) {
   return PV_OK;
 }
 
+// Key preparation on stream ks into ktab, through slot's key scratch (kscr /
+// kscr2, ordered like workspace `slot`: the host pipeline prepares keys in
+// kscr on ws[0]'s stream).  Wide format (radix-256 comb): KEYTAB_WIDE_LANES
+// (128) lanes and 160 KB of scratch per key, verified through k_curve<true, 1>.
+int keys_launch(Device& d, const uint8_t* pk, uint64_t k, uint32_t* ktab, bool wide, hipStream_t ks, int slot) {
+  DevBuf<uint32_t>& scr = slot ? d.kscr2 : d.kscr;
+  if (wide) {
+    HIP_OK(scr.ensure(k * pv::KEYTAB_WIDE_LANES * (uint64_t)pv::KEYTAB_WIDE_SCRATCH));
+    HIP_OK(pv::launch_keys_wide(pk, k, ktab, scr.p, ks));
+  } else {
+    HIP_OK(scr.ensure((k + 63) / 64 * 64 * pv::KEYTAB_SCRATCH));
+    HIP_OK(pv::launch_keys(pk, k, ktab, scr.p, ks));
+  }
+  return PV_OK;
+}
+
+// ... as one use of the slot's workspace on s
+int keys_prepare(Device& d, const uint8_t* pk, uint64_t k, uint32_t* ktab, bool wide, hipStream_t s, int slot) {
+  WsUse use(d.ws[slot], s);
+  if (use.rc) return use.rc;
+  if (const int rc = keys_launch(d, pk, k, ktab, wide, s, slot)) return rc;
+  return use.end();
+}
+
 // prepare keys[0 .. count) (32 bytes each) into key-cache slots [first,
 // first + count) of device d, growing its table (existing slots are kept);
 // synchronous.  d.kc_count is left to the caller.
@@ -1354,14 +1442,12 @@ int kc_prepare(Device& d, const uint8_t* keys, uint64_t first, uint64_t count) {
     d.kc.release();
     d.kc = nb;
   }
-  int rc = ws_begin(d.ws[0], d.stream);
-  if (rc) return rc;
+  WsUse use(d.ws[0], d.stream);
+  if (use.rc) return use.rc;
   HIP_OK(d.kcpk.ensure(32 * count));
   HIP_OK(hipMemcpyAsync(d.kcpk.p, keys, 32 * count, hipMemcpyHostToDevice, d.stream));
-  HIP_OK(d.kscr.ensure((count + 63) / 64 * 64 * pv::KEYTAB_SCRATCH));
-  HIP_OK(pv::launch_keys(d.kcpk.p, count, d.kc.p + first * pv::KEYTAB_WORDS, d.kscr.p, d.stream));
-  rc = ws_end(d.ws[0], d.stream);
-  if (rc) return rc;
+  if (const int rc = keys_launch(d, d.kcpk.p, count, d.kc.p + first * pv::KEYTAB_WORDS, false, d.stream, 0)) return rc;
+  if (const int rc = use.end()) return rc;
   HIP_OK(hipStreamSynchronize(d.stream));
   return PV_OK;
 }
@@ -1371,6 +1457,139 @@ std::vector<Device*> select_devs(uint32_t mask) {
   for (auto& d : g_devs)
     if (mask == 0 || (mask >> d.id) & 1u) v.push_back(&d);
   return v;
+}
+
+// ------------------------------------------------ shared by the entry points
+inline const uint32_t* w32(const uint8_t* p) { return reinterpret_cast<const uint32_t*>(p); }
+inline uint32_t* w32(uint8_t* p) { return reinterpret_cast<uint32_t*>(p); }
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// call-scoped device buffer of the host-buffer entry points
+template <typename T>
+struct TmpBuf {
+  T* p = nullptr;
+  TmpBuf() = default;
+  TmpBuf(const TmpBuf&) = delete;
+  TmpBuf& operator=(const TmpBuf&) = delete;
+  ~TmpBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
+  // allocate and start the upload of n elements on s
+  hipError_t put(const T* host, size_t n, hipStream_t s) {
+    hipError_t e = alloc(n);
+    if (e != hipSuccess || n == 0) return e;
+    return hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s);
+  }
+};
+
+// Declared after the TmpBufs of a host form: once work may be queued on s,
+// every return drains s before the buffers are freed (hipFree would wait too;
+// this says so), and the first error stays the one reported.
+struct StreamDrain {
+  hipStream_t s;
+  bool done = false;
+  int finish() {
+    done = true;
+    HIP_OK(hipStreamSynchronize(s));
+    return PV_OK;
+  }
+  ~StreamDrain() {
+    if (!done) (void)hipStreamSynchronize(s);
+  }
+};
+
+int offsets_ok(const uint64_t* off, uint64_t n, const char* what) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(PV_EINVAL, "%s not monotone at %llu", what, (unsigned long long)i);
+  return PV_OK;
+}
+
+// bytes of src, then the 16 zero bytes the hash kernels read past the last message
+int upload_padded(uint8_t* dst, const uint8_t* src, uint64_t bytes, hipStream_t s) {
+  if (bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemsetAsync(dst + bytes, 0, 16, s));
+  return PV_OK;
+}
+
+// The slice [off[0], off[n]) of a ragged host array (off = NULL with n = 0:
+// empty).  The device gets the slice alone, so its offsets are rebased to
+// zero; rebased() is read by the copy in flight and lives as long as this.
+struct Ragged {
+  const uint64_t* off;
+  const uint64_t n, b0, len;
+  std::vector<uint64_t> offs;
+  Ragged(const uint64_t* off_, uint64_t n_) : off(off_), n(n_), b0(n_ ? off_[0] : 0), len(n_ ? off_[n_] - b0 : 0) {}
+  int check(const char* what) const { return offsets_ok(off, n, what); }
+  const uint64_t* rebased() {
+    offs.resize(n + 1);
+    for (uint64_t k = 0; k <= n; ++k) offs[k] = n ? off[k] - b0 : 0;
+    return offs.data();
+  }
+  // a byte blob and its offsets, into the device's persistent staging buffers ...
+  int stage(const uint8_t* blob, Device& d, hipStream_t s) {
+    HIP_OK(d.blob.ensure(len + 16));
+    HIP_OK(d.off.ensure(n + 1));
+    return upload(blob, d.blob.p, d.off.p, s);
+  }
+  // ... or into call-scoped ones
+  int stage(const uint8_t* blob, TmpBuf<uint8_t>& dblob, TmpBuf<uint64_t>& doff, hipStream_t s) {
+    HIP_OK(dblob.alloc(len + 16));
+    HIP_OK(doff.alloc(n + 1));
+    return upload(blob, dblob.p, doff.p, s);
+  }
+  int upload(const uint8_t* blob, uint8_t* dblob, uint64_t* doff, hipStream_t s) {
+    if (const int rc = upload_padded(dblob, len ? blob + b0 : nullptr, len, s)) return rc;
+    HIP_OK(hipMemcpyAsync(doff, rebased(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    return PV_OK;
+  }
+};
+
+// The pv_verify_*_device(_async) forms.  keyed: ktab / key_idx are arguments
+// of the form; async: the caller names the workspace slot, passes a bitmap and
+// synchronises itself.
+int verify_device(bool keyed, bool wide, bool async, const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk,
+                  const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
+                  uint64_t* bitmap, int device, void* stream, int slot) {
+  Entry en(device, slot);
+  if (const int rc = en.check()) return rc;
+  if (n == 0) return PV_OK;
+  if ((keyed && (!ktab || !key_idx)) || !pk || !sig || !msg_blob || !msg_off || !verdict || (async && !bitmap))
+    return fail(PV_EINVAL, "null device buffer");
+  if (const int rc = en.begin(stream)) return rc;
+  const int rc = enqueue_verify(*en.d, en.d->ws[slot], pk, sig, msg_blob, msg_off, n, verdict, bitmap, en.s, false,
+                                nullptr, nullptr, ktab, key_idx, wide);
+  return async ? rc : en.finish(rc);
+}
+
+// pv_time_verify_device / _keyed_device (ktab = key_idx = NULL: generic)
+int time_verify(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
+                const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict, uint64_t* bitmap,
+                int device, void* stream, int iters, float* ms_hash, float* ms_curve) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (iters <= 0) return fail(PV_EINVAL, "iters must be > 0");
+  if (const int rc = en.begin(stream)) return rc;
+  float a = 0, b = 0;
+  for (int it = 0; it < iters; ++it)
+    if (const int rc = enqueue_verify(*en.d, en.d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, en.s, true,
+                                      &a, &b, ktab, key_idx))
+      return rc;
+  if (ms_hash) *ms_hash = a / iters;
+  if (ms_curve) *ms_curve = b / iters;
+  return PV_OK;
+}
+
+// pv_keys_prepare(_wide)_device(_async)
+int keys_prepare_device(bool wide, bool async, const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream,
+                        int slot) {
+  Entry en(device, slot);
+  if (const int rc = en.check()) return rc;
+  if (k == 0) return PV_OK;
+  if (!pk || !ktab) return fail(PV_EINVAL, "null device buffer");
+  if (const int rc = en.begin(stream)) return rc;
+  const int rc = keys_prepare(*en.d, pk, k, ktab, wide, en.s, slot);
+  return async ? rc : en.finish(rc);
 }
 
 }  // namespace
@@ -1437,9 +1656,8 @@ void pv_shutdown(void) {
 }
 
 int pv_keycache_add(const uint8_t* pk, uint64_t k) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (k == 0) return PV_OK;
   if (!pk) return fail(PV_EINVAL, "null buffer");
   if (g_kc.count() + k > 0xfffffffeull) return fail(PV_EINVAL, "key cache limited to 2^32 - 2 keys");
@@ -1497,9 +1715,8 @@ int pv_device_count(void) {
 int pv_verify_batch(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off,
                     uint64_t n, uint8_t* verdict, uint32_t device_mask, uint32_t flags) {
   if (flags & ~PV_FLAG_DEDUP_KEYS) return fail(PV_EINVAL, "unknown flags 0x%x", flags);
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!pk || !sig || !msg_off || !verdict || (!msg_blob && msg_off[n] != msg_off[0]))
     return fail(PV_EINVAL, "null buffer");
@@ -1547,183 +1764,60 @@ int pv_verify_batch(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg_bl
 
 int pv_verify_batch_device(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off,
                            uint64_t n, uint8_t* verdict, uint64_t* bitmap, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (n == 0) return PV_OK;
-  if (!pk || !sig || !msg_blob || !msg_off || !verdict) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  int rc = enqueue_verify(*d, d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return verify_device(false, false, false, nullptr, nullptr, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device,
+                       stream, 0);
 }
 
 int pv_verify_batch_device_async(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg_blob,
                                  const uint64_t* msg_off, uint64_t n, uint8_t* verdict, uint64_t* bitmap, int device,
                                  void* stream, int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
-  if (n == 0) return PV_OK;
-  if (!pk || !sig || !msg_blob || !msg_off || !verdict || !bitmap) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
-  return enqueue_verify(*d, d->ws[slot], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr);
-}
-
-int pv_verify_keyed_device_async(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
-                                 const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
-                                 uint64_t* bitmap, int device, void* stream, int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
-  if (n == 0) return PV_OK;
-  if (!ktab || !key_idx || !pk || !sig || !msg_blob || !msg_off || !verdict || !bitmap)
-    return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
-  return enqueue_verify(*d, d->ws[slot], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr,
-                        ktab, key_idx);
-}
-
-int pv_keys_prepare_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream, int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
-  if (k == 0) return PV_OK;
-  if (!pk || !ktab) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
-  // the key scratch of slot i is ordered like workspace i (the host pipeline
-  // prepares keys in kscr on ws[0]'s stream)
-  int rc = ws_begin(d->ws[slot], s);
-  if (rc) return rc;
-  DevBuf<uint32_t>& scr = slot ? d->kscr2 : d->kscr;
-  HIP_OK(scr.ensure((k + 63) / 64 * 64 * pv::KEYTAB_SCRATCH));
-  HIP_OK(pv::launch_keys(pk, k, ktab, scr.p, s));
-  return ws_end(d->ws[slot], s);
-}
-
-int pv_keys_prepare_device(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (k == 0) return PV_OK;
-  if (!pk || !ktab) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  int rc = ws_begin(d->ws[0], s);
-  if (rc) return rc;
-  HIP_OK(d->kscr.ensure((k + 63) / 64 * 64 * pv::KEYTAB_SCRATCH));
-  HIP_OK(pv::launch_keys(pk, k, ktab, d->kscr.p, s));
-  rc = ws_end(d->ws[0], s);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return verify_device(false, false, true, nullptr, nullptr, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device,
+                       stream, slot);
 }
 
 int pv_verify_keyed_device(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
                            const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
                            uint64_t* bitmap, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (n == 0) return PV_OK;
-  if (!ktab || !key_idx || !pk || !sig || !msg_blob || !msg_off || !verdict) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  int rc = enqueue_verify(*d, d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr, ktab,
-                          key_idx);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return verify_device(true, false, false, ktab, key_idx, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device,
+                       stream, 0);
 }
 
-// wide key format (radix-256 comb): preparation on KEYTAB_WIDE_LANES (128) lanes
-// per key into kscr / kscr2 (the slot's key scratch, 160 KB per key), verification
-// through k_curve<true, 1>
-static int keys_prepare_wide(Device& d, const uint8_t* pk, uint64_t k, uint32_t* ktab, hipStream_t s, int slot) {
-  int rc = ws_begin(d.ws[slot], s);
-  if (rc) return rc;
-  DevBuf<uint32_t>& scr = slot ? d.kscr2 : d.kscr;
-  HIP_OK(scr.ensure(k * pv::KEYTAB_WIDE_LANES * (uint64_t)pv::KEYTAB_WIDE_SCRATCH));
-  HIP_OK(pv::launch_keys_wide(pk, k, ktab, scr.p, s));
-  return ws_end(d.ws[slot], s);
-}
-
-int pv_keys_prepare_wide_device(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (k == 0) return PV_OK;
-  if (!pk || !ktab) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  const int rc = keys_prepare_wide(*d, pk, k, ktab, s, 0);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
-}
-
-int pv_keys_prepare_wide_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream,
-                                      int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
-  if (k == 0) return PV_OK;
-  if (!pk || !ktab) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
-  return keys_prepare_wide(*d, pk, k, ktab, s, slot);
+int pv_verify_keyed_device_async(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
+                                 const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
+                                 uint64_t* bitmap, int device, void* stream, int slot) {
+  return verify_device(true, false, true, ktab, key_idx, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device,
+                       stream, slot);
 }
 
 int pv_verify_keyed_wide_device(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
                                 const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
                                 uint64_t* bitmap, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (n == 0) return PV_OK;
-  if (!ktab || !key_idx || !pk || !sig || !msg_blob || !msg_off || !verdict) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  int rc = enqueue_verify(*d, d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr, ktab,
-                          key_idx, true);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return verify_device(true, true, false, ktab, key_idx, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device,
+                       stream, 0);
 }
 
 int pv_verify_keyed_wide_device_async(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk,
                                       const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n,
                                       uint8_t* verdict, uint64_t* bitmap, int device, void* stream, int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
-  if (n == 0) return PV_OK;
-  if (!ktab || !key_idx || !pk || !sig || !msg_blob || !msg_off || !verdict || !bitmap)
-    return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
-  return enqueue_verify(*d, d->ws[slot], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr,
-                        ktab, key_idx, true);
+  return verify_device(true, true, true, ktab, key_idx, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device, stream,
+                       slot);
+}
+
+int pv_keys_prepare_device(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream) {
+  return keys_prepare_device(false, false, pk, k, ktab, device, stream, 0);
+}
+
+int pv_keys_prepare_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream, int slot) {
+  return keys_prepare_device(false, true, pk, k, ktab, device, stream, slot);
+}
+
+int pv_keys_prepare_wide_device(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream) {
+  return keys_prepare_device(true, false, pk, k, ktab, device, stream, 0);
+}
+
+int pv_keys_prepare_wide_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, int device, void* stream,
+                                      int slot) {
+  return keys_prepare_device(true, true, pk, k, ktab, device, stream, slot);
 }
 
 // key preparation beside the hash stage: the keys are built on the slot's side
@@ -1731,23 +1825,21 @@ int pv_verify_keyed_wide_device_async(const uint32_t* ktab, const uint32_t* key_
 int pv_verify_keys_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, const uint32_t* key_idx,
                                 const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n,
                                 uint8_t* verdict, uint64_t* bitmap, uint32_t wide, int device, void* stream, int slot) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (slot < 0 || slot > 1) return fail(PV_EINVAL, "slot must be 0 or 1");
+  Entry en(device, slot);
+  if (const int rc = en.check()) return rc;
   if (wide > 1) return fail(PV_EINVAL, "wide must be 0 or 1");
   if (k == 0 && n == 0) return PV_OK;
   if (n > 0 && k == 0) return fail(PV_EINVAL, "signatures without keys");
   if (!pk || !ktab || (n > 0 && (!key_idx || !sig || !msg_blob || !msg_off || !verdict || !bitmap)))
     return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->ws[slot].stream;
+  if (const int rc = en.begin(stream)) return rc;
+  Device* d = en.d;
+  hipStream_t s = en.s;
   Workspace& w = d->ws[slot];
   // the slot's key table and key scratch were last used by its previous batch:
-  // fork after that (ws_begin orders s), join before the curve
-  int rc = ws_begin(w, s);
-  if (rc) return rc;
+  // fork after that (the use orders s), join before the curve
+  WsUse use(w, s);
+  if (use.rc) return use.rc;
   // beside the hash stage only when the key grid is small (less than one wave
   // per SIMD: C3's 25 wide node keys, a latency-bound 50-wave grid): a key
   // grid that fills the GPU (C4's 2^20 keys) competes with k_hash for the
@@ -1758,66 +1850,39 @@ int pv_verify_keys_device_async(const uint8_t* pk, uint64_t k, uint32_t* ktab, c
   hipStream_t ks = side ? d->kside[slot] : s;
   if (side) {
     HIP_OK(hipEventRecord(d->kfork[slot], s));
+    // from here an early return joins the side stream back before the
+    // workspace counts as released (its work writes the key scratch and ktab)
+    use.fork(ks, d->kjoin[slot]);
     HIP_OK(hipStreamWaitEvent(ks, d->kfork[slot], 0));
   }
-  DevBuf<uint32_t>& scr = slot ? d->kscr2 : d->kscr;
-  if (wide) {
-    HIP_OK(scr.ensure(k * pv::KEYTAB_WIDE_LANES * (uint64_t)pv::KEYTAB_WIDE_SCRATCH));
-    HIP_OK(pv::launch_keys_wide(pk, k, ktab, scr.p, ks));
-  } else {
-    HIP_OK(scr.ensure((k + 63) / 64 * 64 * pv::KEYTAB_SCRATCH));
-    HIP_OK(pv::launch_keys(pk, k, ktab, scr.p, ks));
-  }
+  if (const int rc = keys_launch(*d, pk, k, ktab, wide != 0, ks, slot)) return rc;
   if (side) HIP_OK(hipEventRecord(d->kjoin[slot], ks));
   if (n == 0) {
     if (side) HIP_OK(hipStreamWaitEvent(s, d->kjoin[slot], 0));
-    return ws_end(w, s);
+    return use.end();
   }
-  return enqueue_verify(*d, w, pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr, ktab, key_idx,
-                        wide != 0, side ? d->kjoin[slot] : nullptr);
+  const int rc = enqueue_verify(*d, w, pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, false, nullptr, nullptr, ktab,
+                                key_idx, wide != 0, side ? d->kjoin[slot] : nullptr);
+  if (rc == PV_OK) use.open = false;   // enqueue_verify joined and recorded the workspace's last use
+  return rc;
 }
 
 int pv_time_verify_keyed_device(const uint32_t* ktab, const uint32_t* key_idx, const uint8_t* pk, const uint8_t* sig,
                                 const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n, uint8_t* verdict,
                                 uint64_t* bitmap, int device, void* stream, int iters, float* ms_hash,
                                 float* ms_curve) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (iters <= 0) return fail(PV_EINVAL, "iters must be > 0");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  float a = 0, b = 0;
-  for (int it = 0; it < iters; ++it) {
-    int rc = enqueue_verify(*d, d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, true, &a, &b, ktab, key_idx);
-    if (rc) return rc;
-  }
-  if (ms_hash) *ms_hash = a / iters;
-  if (ms_curve) *ms_curve = b / iters;
-  return PV_OK;
+  return time_verify(ktab, key_idx, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device, stream, iters, ms_hash,
+                     ms_curve);
 }
 
 int pv_time_verify_device(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off,
                           uint64_t n, uint8_t* verdict, uint64_t* bitmap, int device, void* stream, int iters,
                           float* ms_hash, float* ms_curve) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
-  if (iters <= 0) return fail(PV_EINVAL, "iters must be > 0");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  float a = 0, b = 0;
-  for (int it = 0; it < iters; ++it) {
-    int rc = enqueue_verify(*d, d->ws[0], pk, sig, msg_blob, msg_off, n, verdict, bitmap, s, true, &a, &b);
-    if (rc) return rc;
-  }
-  if (ms_hash) *ms_hash = a / iters;
-  if (ms_curve) *ms_curve = b / iters;
-  return PV_OK;
+  return time_verify(nullptr, nullptr, pk, sig, msg_blob, msg_off, n, verdict, bitmap, device, stream, iters, ms_hash,
+                     ms_curve);
 }
 
+// (these two look the device up before the guard exists: their own lines)
 int pv_kernel_timing(int device, int enable, float* hash_ms, float* curve_ms, uint64_t* launches) {
   std::lock_guard<std::mutex> lk(g_mu);
   Device* d = find_dev(device);
@@ -1873,10 +1938,9 @@ int pv_set_tuning(const pv_tuning* t) {
 }
 
 int pv_curve_stats(int device, uint32_t* mode, uint64_t* deferred) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  Device* d = en.d;
   if (mode) *mode = d->mode == CurveMode::Half ? PV_CURVE_HALF : d->mode == CurveMode::Full ? PV_CURVE_FULL
                                                                                              : PV_CURVE_GROUPED;
   if (deferred) {
@@ -1894,21 +1958,20 @@ int pv_curve_stats(int device, uint32_t* mode, uint64_t* deferred) {
 int pv_tally_votes_device(const uint8_t* verdict, const uint32_t* sender, const uint64_t* batch_off,
                           uint64_t n_batches, uint32_t n_nodes, uint32_t quorum, uint32_t* votes, uint8_t* reached,
                           int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n_nodes == 0 || n_nodes > 1024) return fail(PV_EINVAL, "n_nodes must be in 1..1024");
   if (n_batches == 0) return PV_OK;
   if (!verdict || !sender || !batch_off || !votes || !reached) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  if (const int rc = en.begin(stream)) return rc;
+  Device* d = en.d;
+  hipStream_t s = en.s;
   HIP_OK(d->tflag.ensure(1));
   HIP_OK(hipMemsetAsync(d->tflag.p, 0, 4, s));
   HIP_OK(pv::launch_tally(verdict, sender, batch_off, n_batches, n_nodes, quorum, votes, reached, d->tflag.p, s));
   uint32_t bad = 0;
   HIP_OK(hipMemcpyAsync(&bad, d->tflag.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
+  if (const int rc = en.finish()) return rc;
   if (bad) return fail(PV_EINVAL, "a sender index is >= n_nodes (%u)", n_nodes);
   return PV_OK;
 }
@@ -1916,30 +1979,27 @@ int pv_tally_votes_device(const uint8_t* verdict, const uint32_t* sender, const 
 int pv_tally_votes_device_async(const uint8_t* verdict, const uint32_t* sender, const uint64_t* batch_off,
                                 uint64_t n_batches, uint32_t n_nodes, uint32_t quorum, uint32_t* votes,
                                 uint8_t* reached, uint32_t* bad, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n_nodes == 0 || n_nodes > 1024) return fail(PV_EINVAL, "n_nodes must be in 1..1024");
   if (!bad) return fail(PV_EINVAL, "null device buffer");
   if (n_batches == 0) return PV_OK;
   if (!verdict || !sender || !batch_off || !votes || !reached) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(pv::launch_tally(verdict, sender, batch_off, n_batches, n_nodes, quorum, votes, reached, bad, s));
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_tally(verdict, sender, batch_off, n_batches, n_nodes, quorum, votes, reached, bad, en.s));
   return PV_OK;
 }
 
 int pv_tally_votes(const uint8_t* verdict, const uint32_t* sender, const uint64_t* batch_off, uint64_t n_batches,
                    uint32_t n_nodes, uint32_t quorum, uint32_t* votes, uint8_t* reached) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n_nodes == 0 || n_nodes > 1024) return fail(PV_EINVAL, "n_nodes must be in 1..1024");
   if (n_batches == 0) return PV_OK;
   if (!verdict || !sender || !batch_off || !votes || !reached) return fail(PV_EINVAL, "null buffer");
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  // (its own rebase: the refusal has no position, unlike offsets_ok's)
   const uint64_t b0 = batch_off[0], m = batch_off[n_batches] - b0;
   std::vector<uint64_t> offs(n_batches + 1);
   for (uint64_t k = 0; k <= n_batches; ++k) {
@@ -1965,36 +2025,30 @@ int pv_tally_votes(const uint8_t* verdict, const uint32_t* sender, const uint64_
                           d.tflag.p, d.stream));
   HIP_OK(hipMemcpyAsync(votes, d.votes.p, n_batches * 4, hipMemcpyDeviceToHost, d.stream));
   HIP_OK(hipMemcpyAsync(reached, d.reached.p, n_batches, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_tally_device(const uint32_t* verdict_bits, const uint32_t* dup_mask, uint64_t n_batches, uint32_t n_nodes,
                     uint32_t quorum, uint8_t* reached, uint32_t* votes, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n_nodes == 0) return fail(PV_EINVAL, "n_nodes must be >= 1");
   if (n_batches == 0) return PV_OK;
   if (!verdict_bits || !reached) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(pv::launch_tally_bits(verdict_bits, dup_mask, n_batches, n_nodes, quorum, votes, reached, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_tally_bits(verdict_bits, dup_mask, n_batches, n_nodes, quorum, votes, reached, en.s));
+  return en.finish();
 }
 
 int pv_tally(const uint32_t* verdict_bits, const uint32_t* dup_mask, uint64_t n_batches, uint32_t n_nodes,
              uint32_t quorum, uint8_t* reached) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n_nodes == 0) return fail(PV_EINVAL, "n_nodes must be >= 1");
   if (n_batches == 0) return PV_OK;
   if (!verdict_bits || !reached) return fail(PV_EINVAL, "null buffer");
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
   const uint64_t words = n_batches * ((n_nodes + 31) / 32);
   HIP_OK(d.tbits.ensure(2 * words));
   HIP_OK(d.reached.ensure(n_batches));
@@ -2003,50 +2057,37 @@ int pv_tally(const uint32_t* verdict_bits, const uint32_t* dup_mask, uint64_t n_
   HIP_OK(pv::launch_tally_bits(d.tbits.p, dup_mask ? d.tbits.p + words : nullptr, n_batches, n_nodes, quorum, nullptr,
                                d.reached.p, d.stream));
   HIP_OK(hipMemcpyAsync(reached, d.reached.p, n_batches, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_sign_batch_device(const uint8_t* seeds, const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n,
                          uint8_t* pk_out, uint8_t* sig_out, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(pv::launch_sign(seeds, msg_blob, msg_off, n, d->btab.p, pk_out, sig_out, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_sign(seeds, msg_blob, msg_off, n, en.d->btab.p, pk_out, sig_out, en.s));
+  return en.finish();
 }
 
 int pv_sign_batch(const uint8_t* seeds, const uint8_t* msg_blob, const uint64_t* msg_off, uint64_t n,
                   uint8_t* pk_out, uint8_t* sig_out) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!seeds || !msg_off || !pk_out || !sig_out) return fail(PV_EINVAL, "null buffer");
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  const uint64_t b0 = msg_off[0], bytes = msg_off[n] - b0;
-  std::vector<uint64_t> offs(n + 1);
-  for (uint64_t k = 0; k <= n; ++k) offs[k] = msg_off[k] - b0;
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  Ragged msgs(msg_off, n);   // (this form does not refuse decreasing offsets)
   HIP_OK(d.tamper.ensure(n * 32));  // seeds staging
-  HIP_OK(d.blob.ensure(bytes + 16));
-  HIP_OK(d.off.ensure(n + 1));
   HIP_OK(d.pk.ensure(n * 32));
   HIP_OK(d.sig.ensure(n * 64));
   HIP_OK(hipMemcpyAsync(d.tamper.p, seeds, n * 32, hipMemcpyHostToDevice, d.stream));
-  if (bytes) HIP_OK(hipMemcpyAsync(d.blob.p, msg_blob + b0, bytes, hipMemcpyHostToDevice, d.stream));
-  HIP_OK(hipMemsetAsync(d.blob.p + bytes, 0, 16, d.stream));
-  HIP_OK(hipMemcpyAsync(d.off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, d.stream));
+  if (const int rc = msgs.stage(msg_blob, d, d.stream)) return rc;
   HIP_OK(pv::launch_sign(d.tamper.p, d.blob.p, d.off.p, n, d.btab.p, d.pk.p, d.sig.p, d.stream));
   HIP_OK(hipMemcpyAsync(pk_out, d.pk.p, n * 32, hipMemcpyDeviceToHost, d.stream));
   HIP_OK(hipMemcpyAsync(sig_out, d.sig.p, n * 64, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 }  // extern "C"
@@ -2057,12 +2098,13 @@ namespace {
 #ifndef PV_MERKLE_TAIL_ON
 #define PV_MERKLE_TAIL_ON 1
 #endif
+// root of the empty tree: hash_empty(), SHA-256 of the empty string (ledger/tree_hasher.py:17-19)
+const uint32_t EMPTY_ROOT[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
+                                0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
 int enqueue_merkle(Device& d, const uint8_t* blob, const uint64_t* off, uint64_t n, uint32_t* leaves, uint32_t* root,
                    hipStream_t s) {
-  if (n == 0) {  // hash_empty(): SHA-256 of the empty string (ledger/tree_hasher.py:17-19)
-    static const uint32_t empty[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
-                                      0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
-    HIP_OK(hipMemcpyAsync(root, empty, 32, hipMemcpyHostToDevice, s));
+  if (n == 0) {
+    HIP_OK(hipMemcpyAsync(root, EMPTY_ROOT, 32, hipMemcpyHostToDevice, s));
     return PV_OK;
   }
   HIP_OK(pv::launch_sha256(blob, off, n, 1, 0x00, d.counter.p, leaves, d.sha256_blocks, s));
@@ -2089,30 +2131,24 @@ extern "C" {
 
 int pv_sha256_batch_device(const uint8_t* blob, const uint64_t* off, uint64_t n, int32_t prefix, uint8_t* digests,
                            int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!blob || !off || !digests) return fail(PV_EINVAL, "null device buffer");
   if (prefix > 255) return fail(PV_EINVAL, "prefix must be -1 (none) or a byte value");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(pv::launch_sha256(blob, off, n, prefix < 0 ? 0 : 1, prefix < 0 ? 0 : (uint32_t)prefix, d->counter.p,
-                           reinterpret_cast<uint32_t*>(digests), d->sha256_blocks, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_sha256(blob, off, n, prefix < 0 ? 0 : 1, prefix < 0 ? 0 : (uint32_t)prefix, en.d->counter.p,
+                           reinterpret_cast<uint32_t*>(digests), en.d->sha256_blocks, en.s));
+  return en.finish();
 }
 
 int pv_merkle_root_device(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* leaf_hashes, uint8_t* root,
                           int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (!root || (n && (!blob || !off))) return fail(PV_EINVAL, "null device buffer");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  if (const int rc = en.begin(stream)) return rc;
+  Device* d = en.d;
   uint32_t* leaves = reinterpret_cast<uint32_t*>(leaf_hashes);
   if (!leaves && n) {
     HIP_OK(d->mk1.ensure((n + 1) / 2 * 8 + n * 8));
@@ -2120,95 +2156,50 @@ int pv_merkle_root_device(const uint8_t* blob, const uint64_t* off, uint64_t n, 
   }
   HIP_OK(d->mk0.ensure((n + 1) / 2 * 8 + 8));
   if (leaf_hashes) HIP_OK(d->mk1.ensure((n + 1) / 2 * 8 + 8));
-  int rc = enqueue_merkle(*d, blob, off, n, leaves, reinterpret_cast<uint32_t*>(root), s);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return en.finish(enqueue_merkle(*d, blob, off, n, leaves, reinterpret_cast<uint32_t*>(root), en.s));
 }
 
 int pv_merkle_root(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* root, uint8_t* leaf_hashes) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (!root || (n && (!off || (!blob && off[n] != off[0])))) return fail(PV_EINVAL, "null buffer");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(PV_EINVAL, "off not monotone at %llu", (unsigned long long)i);
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  const uint64_t b0 = n ? off[0] : 0, bytes = n ? off[n] - b0 : 0;
-  std::vector<uint64_t> offs(n + 1);
-  for (uint64_t k = 0; k <= n; ++k) offs[k] = n ? off[k] - b0 : 0;
-  HIP_OK(d.blob.ensure(bytes + 16));
-  HIP_OK(d.off.ensure(n + 1));
+  Ragged leaf(off, n);
+  if (const int rc = leaf.check("off")) return rc;
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
   HIP_OK(d.mk0.ensure((n + 1) / 2 * 8 + 8));
   HIP_OK(d.mk1.ensure((n + 1) / 2 * 8 + n * 8 + 8));
   uint32_t* leaves = d.mk1.p + (n + 1) / 2 * 8;
   uint32_t* droot = d.mk0.p + (n + 1) / 2 * 8;
-  if (bytes) HIP_OK(hipMemcpyAsync(d.blob.p, blob + b0, bytes, hipMemcpyHostToDevice, d.stream));
-  HIP_OK(hipMemsetAsync(d.blob.p + bytes, 0, 16, d.stream));
-  HIP_OK(hipMemcpyAsync(d.off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, d.stream));
-  int rc = enqueue_merkle(d, d.blob.p, d.off.p, n, leaves, droot, d.stream);
-  if (rc) return rc;
+  if (const int rc = leaf.stage(blob, d, d.stream)) return rc;
+  if (const int rc = enqueue_merkle(d, d.blob.p, d.off.p, n, leaves, droot, d.stream)) return rc;
   HIP_OK(hipMemcpyAsync(root, droot, 32, hipMemcpyDeviceToHost, d.stream));
   if (leaf_hashes && n) HIP_OK(hipMemcpyAsync(leaf_hashes, leaves, n * 32, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_sha256_batch(const uint8_t* blob, const uint64_t* off, uint64_t n, int32_t prefix, uint8_t* digests) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!off || !digests || (!blob && off[n] != off[0])) return fail(PV_EINVAL, "null buffer");
   if (prefix > 255) return fail(PV_EINVAL, "prefix must be -1 (none) or a byte value");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(PV_EINVAL, "off not monotone at %llu", (unsigned long long)i);
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  const uint64_t b0 = off[0], bytes = off[n] - b0;
-  std::vector<uint64_t> offs(n + 1);
-  for (uint64_t k = 0; k <= n; ++k) offs[k] = off[k] - b0;
-  HIP_OK(d.blob.ensure(bytes + 16));
-  HIP_OK(d.off.ensure(n + 1));
+  Ragged msgs(off, n);
+  if (const int rc = msgs.check("off")) return rc;
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
   HIP_OK(d.mk0.ensure(n * 8));
-  if (bytes) HIP_OK(hipMemcpyAsync(d.blob.p, blob + b0, bytes, hipMemcpyHostToDevice, d.stream));
-  HIP_OK(hipMemsetAsync(d.blob.p + bytes, 0, 16, d.stream));
-  HIP_OK(hipMemcpyAsync(d.off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, d.stream));
+  if (const int rc = msgs.stage(blob, d, d.stream)) return rc;
   HIP_OK(pv::launch_sha256(d.blob.p, d.off.p, n, prefix < 0 ? 0 : 1, prefix < 0 ? 0 : (uint32_t)prefix, d.counter.p,
                            d.mk0.p, d.sha256_blocks, d.stream));
   HIP_OK(hipMemcpyAsync(digests, d.mk0.p, n * 32, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 }  // extern "C"
 
 // ------------------------------------------ Merkle audit paths / consistency
 namespace {
-
-// call-scoped device buffer of the host-buffer entry points
-template <typename T>
-struct TmpBuf {
-  T* p = nullptr;
-  TmpBuf() = default;
-  TmpBuf(const TmpBuf&) = delete;
-  TmpBuf& operator=(const TmpBuf&) = delete;
-  ~TmpBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
-  // allocate and start the upload of n elements on s
-  hipError_t put(const T* host, size_t n, hipStream_t s) {
-    hipError_t e = alloc(n);
-    if (e != hipSuccess || n == 0) return e;
-    return hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s);
-  }
-};
-
-inline const uint32_t* w32(const uint8_t* p) { return reinterpret_cast<const uint32_t*>(p); }
-inline uint32_t* w32(uint8_t* p) { return reinterpret_cast<uint32_t*>(p); }
-inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 int merkle_blocks(const Device& d) { return d.cu_count * 32; }
 
@@ -2315,20 +2306,14 @@ int tree_rebuild(MerkleTree& t, uint64_t n_new, hipStream_t s) {
   return PV_OK;
 }
 
-// resolve a handle to its tree and device, and make the device current
-int tree_enter(int32_t handle, MerkleTree** t, Device** d) {
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+// resolve a handle to its tree and point the (host-form) entry scope at the
+// tree's device; en.begin() then makes it current
+int tree_enter(Entry& en, int32_t handle, MerkleTree** t) {
+  if (const int rc = en.check()) return rc;
   *t = find_tree(handle);
   if (!*t) return fail(PV_EINVAL, "no Merkle tree with handle %d", (int)handle);
-  *d = find_dev((*t)->dev);
-  if (!*d) return fail(PV_EINVAL, "the device of Merkle tree %d is gone", (int)handle);
-  HIP_OK(hipSetDevice((*d)->ord));
-  return PV_OK;
-}
-
-int offsets_ok(const uint64_t* off, uint64_t n, const char* what) {
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(PV_EINVAL, "%s not monotone at %llu", what, (unsigned long long)i);
+  en.d = find_dev((*t)->dev);
+  if (!en.d) return fail(PV_EINVAL, "the device of Merkle tree %d is gone", (int)handle);
   return PV_OK;
 }
 
@@ -2356,10 +2341,8 @@ int pv_merkle_verify_inclusion_device(const uint8_t* leaf_hashes, const uint8_t*
                                       const uint64_t* proof_off, const uint8_t* roots, const uint32_t* root_idx,
                                       uint64_t n_roots, uint64_t n, uint8_t* status, uint8_t* computed,
                                       uint64_t* stop_index, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if ((!leaf_hashes && (!leaf_blob || !leaf_off)) || !index || !tree_size || !nodes || !proof_off || !roots ||
       !status || !computed || !stop_index)
@@ -2367,13 +2350,9 @@ int pv_merkle_verify_inclusion_device(const uint8_t* leaf_hashes, const uint8_t*
   if (root_idx && n_roots == 0) return fail(PV_EINVAL, "root_idx without roots");
   if (misaligned16(leaf_hashes) || misaligned16(nodes) || misaligned16(roots) || misaligned16(computed))
     return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  int rc = enqueue_verify_incl(*d, w32(leaf_hashes), leaf_blob, leaf_off, index, tree_size, w32(nodes), proof_off,
-                               w32(roots), root_idx, n, status, w32(computed), stop_index, s);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  return en.finish(enqueue_verify_incl(*en.d, w32(leaf_hashes), leaf_blob, leaf_off, index, tree_size, w32(nodes),
+                                       proof_off, w32(roots), root_idx, n, status, w32(computed), stop_index, en.s));
 }
 
 int pv_merkle_verify_inclusion(const uint8_t* leaf_hashes, const uint8_t* leaf_blob, const uint64_t* leaf_off,
@@ -2381,68 +2360,51 @@ int pv_merkle_verify_inclusion(const uint8_t* leaf_hashes, const uint8_t* leaf_b
                                const uint64_t* proof_off, const uint8_t* roots, const uint32_t* root_idx,
                                uint64_t n_roots, uint64_t n, uint8_t* status, uint8_t* computed,
                                uint64_t* stop_index) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if ((!leaf_hashes && !leaf_off) || !index || !tree_size || !proof_off || !roots || !status || !computed ||
       !stop_index)
     return fail(PV_EINVAL, "null buffer");
-  int rc = offsets_ok(proof_off, n, "proof_off");
-  if (rc) return rc;
-  const uint64_t p0 = proof_off[0], total = proof_off[n] - p0;
-  if (total && !nodes) return fail(PV_EINVAL, "null buffer");
-  uint64_t b0 = 0, bytes = 0;
-  if (!leaf_hashes) {
-    rc = offsets_ok(leaf_off, n, "leaf_off");
-    if (rc) return rc;
-    b0 = leaf_off[0];
-    bytes = leaf_off[n] - b0;
-    if (bytes && !leaf_blob) return fail(PV_EINVAL, "null buffer");
-  }
+  Ragged proofs(proof_off, n);   // in nodes
+  if (const int rc = proofs.check("proof_off")) return rc;
+  if (proofs.len && !nodes) return fail(PV_EINVAL, "null buffer");
+  Ragged leaf(leaf_hashes ? nullptr : leaf_off, leaf_hashes ? 0 : n);   // leaf mode only
+  if (const int rc = leaf.check("leaf_off")) return rc;
+  if (leaf.len && !leaf_blob) return fail(PV_EINVAL, "null buffer");
   if (root_idx)
     for (uint64_t i = 0; i < n; ++i)
       if (root_idx[i] >= n_roots)
         return fail(PV_EINVAL, "root_idx[%llu] = %u is not below n_roots %llu", (unsigned long long)i, root_idx[i],
                     (unsigned long long)n_roots);
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  hipStream_t s = d.stream;
-  std::vector<uint64_t> poff(n + 1), loff;
-  for (uint64_t i = 0; i <= n; ++i) poff[i] = proof_off[i] - p0;
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
   TmpBuf<uint8_t> dleaf, dblob, dnodes, droots, dstatus, dcomp;
   TmpBuf<uint64_t> dloff, dindex, dsize, dpoff, dstop;
   TmpBuf<uint32_t> dridx;
+  StreamDrain tail{s};
   if (leaf_hashes) {
     HIP_OK(dleaf.put(leaf_hashes, n * 32, s));
-  } else {
-    loff.resize(n + 1);
-    for (uint64_t i = 0; i <= n; ++i) loff[i] = leaf_off[i] - b0;
-    HIP_OK(dblob.alloc(bytes + 16));
-    if (bytes) HIP_OK(hipMemcpyAsync(dblob.p, leaf_blob + b0, bytes, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemsetAsync(dblob.p + bytes, 0, 16, s));
-    HIP_OK(dloff.put(loff.data(), n + 1, s));
+  } else if (const int rc = leaf.stage(leaf_blob, dblob, dloff, s)) {
+    return rc;
   }
   HIP_OK(dindex.put(index, n, s));
   HIP_OK(dsize.put(tree_size, n, s));
-  HIP_OK(dnodes.put(total ? nodes + p0 * 32 : nullptr, total * 32, s));
-  HIP_OK(dpoff.put(poff.data(), n + 1, s));
+  HIP_OK(dnodes.put(proofs.len ? nodes + proofs.b0 * 32 : nullptr, proofs.len * 32, s));
+  HIP_OK(dpoff.put(proofs.rebased(), n + 1, s));
   HIP_OK(droots.put(roots, (root_idx ? n_roots : n) * 32, s));
   if (root_idx) HIP_OK(dridx.put(root_idx, n, s));
   HIP_OK(dstatus.alloc(n));
   HIP_OK(dcomp.alloc(n * 32));
   HIP_OK(dstop.alloc(n));
-  rc = enqueue_verify_incl(d, leaf_hashes ? w32(dleaf.p) : nullptr, dblob.p, dloff.p, dindex.p, dsize.p,
-                           w32(dnodes.p), dpoff.p, w32(droots.p), dridx.p, n, dstatus.p, w32(dcomp.p), dstop.p, s);
-  if (rc) {
-    (void)hipStreamSynchronize(s);
+  if (const int rc = enqueue_verify_incl(*en.d, leaf_hashes ? w32(dleaf.p) : nullptr, dblob.p, dloff.p, dindex.p,
+                                         dsize.p, w32(dnodes.p), dpoff.p, w32(droots.p), dridx.p, n, dstatus.p,
+                                         w32(dcomp.p), dstop.p, s))
     return rc;
-  }
   HIP_OK(hipMemcpyAsync(status, dstatus.p, n, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(computed, dcomp.p, n * 32, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(stop_index, dstop.p, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return tail.finish();
 }
 
 int pv_merkle_verify_consistency_device(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
@@ -2450,10 +2412,8 @@ int pv_merkle_verify_consistency_device(const uint64_t* old_size, const uint64_t
                                         const uint32_t* new_root_idx, uint64_t n_roots, const uint8_t* nodes,
                                         const uint64_t* proof_off, uint64_t n, uint8_t* status, uint8_t* old_computed,
                                         uint8_t* new_computed, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!old_size || !new_size || !old_roots || !new_roots || !nodes || !proof_off || !status || !old_computed ||
       !new_computed)
@@ -2464,45 +2424,39 @@ int pv_merkle_verify_consistency_device(const uint64_t* old_size, const uint64_t
   if (misaligned16(old_roots) || misaligned16(new_roots) || misaligned16(nodes) || misaligned16(old_computed) ||
       misaligned16(new_computed))
     return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  if (const int rc = en.begin(stream)) return rc;
   HIP_OK(pv::launch_merkle_verify_cons(old_size, new_size, w32(old_roots), w32(new_roots), old_root_idx, new_root_idx,
                                        w32(nodes), proof_off, n, status, w32(old_computed), w32(new_computed),
-                                       merkle_blocks(*d), s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+                                       merkle_blocks(*en.d), en.s));
+  return en.finish();
 }
 
 int pv_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
                                  const uint8_t* new_roots, const uint32_t* old_root_idx, const uint32_t* new_root_idx,
                                  uint64_t n_roots, const uint8_t* nodes, const uint64_t* proof_off, uint64_t n,
                                  uint8_t* status, uint8_t* old_computed, uint8_t* new_computed) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!old_size || !new_size || !old_roots || !new_roots || !proof_off || !status || !old_computed || !new_computed)
     return fail(PV_EINVAL, "null buffer");
   if ((old_root_idx == nullptr) != (new_root_idx == nullptr))
     return fail(PV_EINVAL, "old_root_idx and new_root_idx go together");
-  int rc = offsets_ok(proof_off, n, "proof_off");
-  if (rc) return rc;
-  const uint64_t p0 = proof_off[0], total = proof_off[n] - p0;
-  if (total && !nodes) return fail(PV_EINVAL, "null buffer");
+  Ragged proofs(proof_off, n);   // in nodes
+  if (const int rc = proofs.check("proof_off")) return rc;
+  if (proofs.len && !nodes) return fail(PV_EINVAL, "null buffer");
   if (old_root_idx)
     for (uint64_t i = 0; i < n; ++i)
       if (old_root_idx[i] >= n_roots || new_root_idx[i] >= n_roots)
         return fail(PV_EINVAL, "a root index of pair %llu is not below n_roots %llu", (unsigned long long)i,
                     (unsigned long long)n_roots);
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  hipStream_t s = d.stream;
-  std::vector<uint64_t> poff(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) poff[i] = proof_off[i] - p0;
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
   const uint64_t nr = old_root_idx ? n_roots : n;
   TmpBuf<uint8_t> dnodes, dro, drn, dstatus, dco, dcn;
   TmpBuf<uint64_t> dold, dnew, dpoff;
   TmpBuf<uint32_t> dio, din;
+  StreamDrain tail{s};
   HIP_OK(dold.put(old_size, n, s));
   HIP_OK(dnew.put(new_size, n, s));
   HIP_OK(dro.put(old_roots, nr * 32, s));
@@ -2511,26 +2465,24 @@ int pv_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_s
     HIP_OK(dio.put(old_root_idx, n, s));
     HIP_OK(din.put(new_root_idx, n, s));
   }
-  HIP_OK(dnodes.put(total ? nodes + p0 * 32 : nullptr, total * 32, s));
-  HIP_OK(dpoff.put(poff.data(), n + 1, s));
+  HIP_OK(dnodes.put(proofs.len ? nodes + proofs.b0 * 32 : nullptr, proofs.len * 32, s));
+  HIP_OK(dpoff.put(proofs.rebased(), n + 1, s));
   HIP_OK(dstatus.alloc(n));
   HIP_OK(dco.alloc(n * 32));
   HIP_OK(dcn.alloc(n * 32));
   HIP_OK(pv::launch_merkle_verify_cons(dold.p, dnew.p, w32(dro.p), w32(drn.p), dio.p, din.p, w32(dnodes.p), dpoff.p, n,
-                                       dstatus.p, w32(dco.p), w32(dcn.p), merkle_blocks(d), s));
+                                       dstatus.p, w32(dco.p), w32(dcn.p), merkle_blocks(*en.d), s));
   HIP_OK(hipMemcpyAsync(status, dstatus.p, n, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(old_computed, dco.p, n * 32, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(new_computed, dcn.p, n * 32, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return tail.finish();
 }
 
 int pv_merkle_tree_create(uint64_t capacity_hint, int device, int32_t* handle) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
+  Entry en(device);
   if (!handle) return fail(PV_EINVAL, "null pointer");
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  if (const int rc = en.check()) return rc;
+  Device* d = en.d;
   if (capacity_hint > (1ull << 40)) return fail(PV_EINVAL, "capacity_hint above 2^40 leaves");
   size_t slot = 0;
   while (slot < g_trees.size() && g_trees[slot].live) ++slot;
@@ -2543,7 +2495,7 @@ int pv_merkle_tree_create(uint64_t capacity_hint, int device, int32_t* handle) {
   t.live = true;
   t.dev = d->id;
   t.hint = capacity_hint ? capacity_hint : 1;
-  HIP_OK(hipSetDevice(d->ord));
+  if (const int rc = en.begin()) return rc;
   int rc = tree_grow(t, 0, t.hint, d->stream);
   if (rc == PV_OK) rc = tree_rebuild(t, 0, d->stream);   // uploads the level table
   if (rc == PV_OK) {
@@ -2570,23 +2522,16 @@ int pv_merkle_tree_free(int32_t handle) {
 // append k leaf hashes from host or device memory and rebuild the parents they change
 static int tree_extend_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, hipMemcpyKind kind,
                               void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
+  Entry en;
   MerkleTree* t;
-  Device* d;
-  int rc = tree_enter(handle, &t, &d);
-  if (rc) return rc;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
   if (k == 0) return PV_OK;
   if (!leaf_hashes) return fail(PV_EINVAL, "null buffer");
   if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  rc = tree_grow(*t, 0, t->n + k, s);
-  if (rc) return rc;
-  HIP_OK(hipMemcpyAsync(t->lv[0] + 8 * t->n, leaf_hashes, k * 32, kind, s));
-  rc = tree_rebuild(*t, t->n + k, s);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  if (const int rc = tree_grow(*t, 0, t->n + k, en.s)) return rc;
+  HIP_OK(hipMemcpyAsync(t->lv[0] + 8 * t->n, leaf_hashes, k * 32, kind, en.s));
+  return en.finish(tree_rebuild(*t, t->n + k, en.s));
 }
 
 int pv_merkle_tree_extend_hashes_device(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, void* stream) {
@@ -2598,55 +2543,34 @@ int pv_merkle_tree_extend_hashes(int32_t handle, const uint8_t* leaf_hashes, uin
 }
 
 int pv_merkle_tree_extend(int32_t handle, const uint8_t* blob, const uint64_t* off, uint64_t k) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
+  Entry en;
   MerkleTree* t;
-  Device* d;
-  int rc = tree_enter(handle, &t, &d);
-  if (rc) return rc;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
   if (k == 0) return PV_OK;
   if (!off || (!blob && off[k] != off[0])) return fail(PV_EINVAL, "null buffer");
   if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
-  rc = offsets_ok(off, k, "off");
-  if (rc) return rc;
-  hipStream_t s = d->stream;
-  const uint64_t b0 = off[0], bytes = off[k] - b0;
-  std::vector<uint64_t> offs(k + 1);
-  for (uint64_t i = 0; i <= k; ++i) offs[i] = off[i] - b0;
-  HIP_OK(d->blob.ensure(bytes + 16));
-  HIP_OK(d->off.ensure(k + 1));
-  if (bytes) HIP_OK(hipMemcpyAsync(d->blob.p, blob + b0, bytes, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemsetAsync(d->blob.p + bytes, 0, 16, s));
-  HIP_OK(hipMemcpyAsync(d->off.p, offs.data(), (k + 1) * 8, hipMemcpyHostToDevice, s));
-  rc = tree_grow(*t, 0, t->n + k, s);
-  if (rc) return rc;
+  Ragged leaf(off, k);
+  if (const int rc = leaf.check("off")) return rc;
+  if (const int rc = en.begin()) return rc;
+  Device* d = en.d;
+  hipStream_t s = en.s;
+  if (const int rc = leaf.stage(blob, *d, s)) return rc;
+  if (const int rc = tree_grow(*t, 0, t->n + k, s)) return rc;
   HIP_OK(pv::launch_sha256(d->blob.p, d->off.p, k, 1, 0x00, d->counter.p, t->lv[0] + 8 * t->n, d->sha256_blocks, s));
-  rc = tree_rebuild(*t, t->n + k, s);
-  if (rc) return rc;
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return en.finish(tree_rebuild(*t, t->n + k, s));
 }
 
 int pv_merkle_tree_info(int32_t handle, uint64_t* n, uint32_t* depth, uint8_t* root) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
+  Entry en;
   MerkleTree* t;
-  Device* d;
-  int rc = tree_enter(handle, &t, &d);
-  if (rc) return rc;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
   if (n) *n = t->n;
   if (depth) *depth = t->depth;
-  if (root) {
-    if (t->n == 0) {   // hash_empty(): SHA-256 of the empty string (ledger/tree_hasher.py:17-19)
-      static const uint32_t empty[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
-                                        0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
-      memcpy(root, empty, 32);
-    } else {
-      HIP_OK(hipMemcpyAsync(root, t->lv[t->depth], 32, hipMemcpyDeviceToHost, d->stream));
-      HIP_OK(hipStreamSynchronize(d->stream));
-    }
-  }
-  return PV_OK;
+  if (root && t->n == 0) memcpy(root, EMPTY_ROOT, 32);
+  if (!root || t->n == 0) return PV_OK;
+  if (const int rc = en.begin()) return rc;
+  HIP_OK(hipMemcpyAsync(root, t->lv[t->depth], 32, hipMemcpyDeviceToHost, en.s));
+  return en.finish();
 }
 
 // k requests over a resident tree: audit paths (a = index, b = tree_size, roots_out given) or
@@ -2655,47 +2579,47 @@ int pv_merkle_tree_info(int32_t handle, uint64_t* n, uint32_t* depth, uint8_t* r
 // refused request in its length.
 static int tree_requests(int32_t handle, const uint64_t* a, const uint64_t* b, uint64_t k, uint8_t* nodes_out,
                          uint32_t* len_out, uint8_t* roots_out, bool paths, bool host, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
+  Entry en;
   MerkleTree* t;
-  Device* d;
-  int rc = tree_enter(handle, &t, &d);
-  if (rc) return rc;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
   if (k == 0) return PV_OK;
   if (!a || !b || !nodes_out || !len_out || (paths && !roots_out)) return fail(PV_EINVAL, "null buffer");
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  const uint64_t node_bytes = k * ((uint64_t)t->depth + 1) * 32;
-  TmpBuf<uint64_t> da, db;
-  TmpBuf<uint8_t> dnodes, droots;
-  TmpBuf<uint32_t> dlen;
-  const uint64_t *pa = a, *pb = b;
-  uint8_t *pn = nodes_out, *pr = roots_out;
-  uint32_t* pl = len_out;
   if (host) {
     for (uint64_t i = 0; i < k; ++i)   // refused before any launch, never clamped
       if (paths ? (b[i] == 0 || b[i] > t->n || a[i] >= b[i]) : (a[i] > b[i] || b[i] > t->n))
         return fail(PV_EINVAL, "request %llu: (%llu, %llu) outside a tree of %llu leaves", (unsigned long long)i,
                     (unsigned long long)a[i], (unsigned long long)b[i], (unsigned long long)t->n);
+  } else if (misaligned16(nodes_out) || misaligned16(roots_out)) {
+    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  }
+  if (const int rc = en.begin(stream)) return rc;
+  hipStream_t s = en.s;
+  const uint64_t node_bytes = k * ((uint64_t)t->depth + 1) * 32;
+  TmpBuf<uint64_t> da, db;
+  TmpBuf<uint8_t> dnodes, droots;
+  TmpBuf<uint32_t> dlen;
+  StreamDrain tail{s};
+  const uint64_t *pa = a, *pb = b;
+  uint8_t *pn = nodes_out, *pr = roots_out;
+  uint32_t* pl = len_out;
+  if (host) {
     HIP_OK(da.put(a, k, s));
     HIP_OK(db.put(b, k, s));
     HIP_OK(dnodes.alloc(node_bytes));
     HIP_OK(droots.alloc(k * 32));
     HIP_OK(dlen.alloc(k));
     pa = da.p, pb = db.p, pn = dnodes.p, pr = droots.p, pl = dlen.p;
-  } else if (misaligned16(nodes_out) || misaligned16(roots_out)) {
-    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
   }
   if (paths)
-    HIP_OK(pv::launch_merkle_paths(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, w32(pr), merkle_blocks(*d), s));
+    HIP_OK(pv::launch_merkle_paths(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, w32(pr), merkle_blocks(*en.d), s));
   else
-    HIP_OK(pv::launch_merkle_cons_proofs(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, merkle_blocks(*d), s));
+    HIP_OK(pv::launch_merkle_cons_proofs(t->table, t->n, t->depth, pa, pb, k, w32(pn), pl, merkle_blocks(*en.d), s));
   if (host) {
     HIP_OK(hipMemcpyAsync(nodes_out, pn, node_bytes, hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(len_out, pl, k * 4, hipMemcpyDeviceToHost, s));
     if (paths) HIP_OK(hipMemcpyAsync(roots_out, pr, k * 32, hipMemcpyDeviceToHost, s));
   }
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return tail.finish();
 }
 
 int pv_merkle_audit_paths_device(int32_t handle, const uint64_t* index, const uint64_t* tree_size, uint64_t k,
@@ -2721,44 +2645,31 @@ int pv_merkle_consistency_proofs(int32_t handle, const uint64_t* first, const ui
 // ------------------------------------------------ SHA3-256 / state proofs
 int pv_sha3_256_batch_device(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* digests, int device,
                              void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!blob || !off || !digests) return fail(PV_EINVAL, "null device buffer");
   if (misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
   if (reinterpret_cast<uintptr_t>(blob) & 3u) return fail(PV_EINVAL, "blob must be 4-byte aligned");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(pv::launch_sha3_256(blob, off, off + 1, n, d->counter.p, w32(digests), d->sha3_blocks, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_sha3_256(blob, off, off + 1, n, en.d->counter.p, w32(digests), en.d->sha3_blocks, en.s));
+  return en.finish();
 }
 
 int pv_sha3_256_batch(const uint8_t* blob, const uint64_t* off, uint64_t n, uint8_t* digests) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (n == 0) return PV_OK;
   if (!off || !digests || (!blob && off[n] != off[0])) return fail(PV_EINVAL, "null buffer");
-  int rc = offsets_ok(off, n, "off");
-  if (rc) return rc;
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  const uint64_t b0 = off[0], bytes = off[n] - b0;
-  std::vector<uint64_t> offs(n + 1);
-  for (uint64_t k = 0; k <= n; ++k) offs[k] = off[k] - b0;
-  HIP_OK(d.blob.ensure(bytes + 16));
-  HIP_OK(d.off.ensure(n + 1));
+  Ragged msgs(off, n);
+  if (const int rc = msgs.check("off")) return rc;
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
   HIP_OK(d.mk0.ensure(n * 8));
-  if (bytes) HIP_OK(hipMemcpyAsync(d.blob.p, blob + b0, bytes, hipMemcpyHostToDevice, d.stream));
-  HIP_OK(hipMemsetAsync(d.blob.p + bytes, 0, 16, d.stream));
-  HIP_OK(hipMemcpyAsync(d.off.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, d.stream));
+  if (const int rc = msgs.stage(blob, d, d.stream)) return rc;
   HIP_OK(pv::launch_sha3_256(d.blob.p, d.off.p, d.off.p + 1, n, d.counter.p, d.mk0.p, d.sha3_blocks, d.stream));
   HIP_OK(hipMemcpyAsync(digests, d.mk0.p, n * 32, hipMemcpyDeviceToHost, d.stream));
-  HIP_OK(hipStreamSynchronize(d.stream));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_rlp_split_list(const uint8_t* rlp, uint64_t len, uint64_t* item_beg, uint64_t* item_end, uint64_t cap,
@@ -2774,10 +2685,8 @@ int pv_state_proof_verify_device(const uint8_t* node_blob, const uint64_t* node_
                                  const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
                                  const uint64_t* val_off, uint64_t N, uint64_t P, uint64_t Q, uint8_t* status,
                                  uint8_t* node_digests, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (Q == 0) return PV_OK;
   if (!proof_first || !roots || !proof_idx || !key_off || !val_off || !status ||
       (N && (!node_blob || !node_beg || !node_end || !node_digests)))
@@ -2786,13 +2695,13 @@ int pv_state_proof_verify_device(const uint8_t* node_blob, const uint64_t* node_
   if (misaligned16(node_digests) || (reinterpret_cast<uintptr_t>(roots) & 3u) ||
       (reinterpret_cast<uintptr_t>(node_blob) & 3u))
     return fail(PV_EINVAL, "node_digests must be 16-byte aligned, roots and node_blob 4-byte aligned");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  if (const int rc = en.begin(stream)) return rc;
+  Device* d = en.d;
+  hipStream_t s = en.s;
   HIP_OK(pv::launch_sha3_256(node_blob, node_beg, node_end, N, d->counter.p, w32(node_digests), d->sha3_blocks, s));
   HIP_OK(pv::launch_trie_verify(node_blob, node_beg, node_end, w32(node_digests), proof_first, w32(roots), P,
                                 proof_idx, key_blob, key_off, val_blob, val_off, Q, status, merkle_blocks(*d), s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_state_proof_verify(const uint8_t* node_blob, uint64_t node_blob_len, const uint64_t* node_beg,
@@ -2800,25 +2709,21 @@ int pv_state_proof_verify(const uint8_t* node_blob, uint64_t node_blob_len, cons
                           const uint32_t* proof_idx, const uint8_t* key_blob, const uint64_t* key_off,
                           const uint8_t* val_blob, const uint64_t* val_off, uint64_t N, uint64_t P, uint64_t Q,
                           uint8_t* status) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  if (g_devs.empty()) return fail(PV_ENOTINIT, "pv_init has not been called");
+  Entry en;
+  if (const int rc = en.check()) return rc;
   if (Q == 0) return PV_OK;
   if (!proof_first || !roots || !proof_idx || !key_off || !val_off || !status ||
       (N && (!node_beg || !node_end)) || (node_blob_len && !node_blob))
     return fail(PV_EINVAL, "null buffer");
   if (P == 0) return fail(PV_EINVAL, "queries without proofs");
-  int rc = offsets_ok(key_off, Q, "key_off");
-  if (rc) return rc;
-  rc = offsets_ok(val_off, Q, "val_off");
-  if (rc) return rc;
-  const uint64_t k0 = key_off[0], kbytes = key_off[Q] - k0, v0 = val_off[0], vbytes = val_off[Q] - v0;
-  if ((kbytes && !key_blob) || (vbytes && !val_blob)) return fail(PV_EINVAL, "null buffer");
+  Ragged keys(key_off, Q), vals(val_off, Q);
+  if (const int rc = keys.check("key_off")) return rc;
+  if (const int rc = vals.check("val_off")) return rc;
+  if ((keys.len && !key_blob) || (vals.len && !val_blob)) return fail(PV_EINVAL, "null buffer");
   for (uint64_t j = 0; j < N; ++j)
     if (node_beg[j] > node_end[j] || node_end[j] > node_blob_len)
       return fail(PV_EINVAL, "node %llu lies outside the blob", (unsigned long long)j);
-  rc = offsets_ok(proof_first, P, "proof_first");
-  if (rc) return rc;
+  if (const int rc = offsets_ok(proof_first, P, "proof_first")) return rc;
   if (proof_first[P] != N)
     return fail(PV_EINVAL, "proof_first ends at %llu, not at N = %llu", (unsigned long long)proof_first[P],
                 (unsigned long long)N);
@@ -2826,85 +2731,68 @@ int pv_state_proof_verify(const uint8_t* node_blob, uint64_t node_blob_len, cons
     if (proof_idx[i] >= P)
       return fail(PV_EINVAL, "proof_idx[%llu] = %u is not below P = %llu", (unsigned long long)i, proof_idx[i],
                   (unsigned long long)P);
-  Device& d = g_devs[0];
-  HIP_OK(hipSetDevice(d.ord));
-  hipStream_t s = d.stream;
-  std::vector<uint64_t> koff(Q + 1), voff(Q + 1);
-  for (uint64_t i = 0; i <= Q; ++i) {
-    koff[i] = key_off[i] - k0;
-    voff[i] = val_off[i] - v0;
-  }
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  hipStream_t s = en.s;
   TmpBuf<uint8_t> dblob, droots, dkeys, dvals, dstatus, ddig;
   TmpBuf<uint64_t> dbeg, dend, dfirst, dkoff, dvoff;
   TmpBuf<uint32_t> dpidx;
+  StreamDrain tail{s};
   HIP_OK(dblob.alloc(node_blob_len + 16));
-  if (node_blob_len) HIP_OK(hipMemcpyAsync(dblob.p, node_blob, node_blob_len, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemsetAsync(dblob.p + node_blob_len, 0, 16, s));
+  if (const int rc = upload_padded(dblob.p, node_blob, node_blob_len, s)) return rc;
   HIP_OK(dbeg.put(node_beg, N, s));
   HIP_OK(dend.put(node_end, N, s));
   HIP_OK(dfirst.put(proof_first, P + 1, s));
   HIP_OK(droots.put(roots, P * 32, s));
   HIP_OK(dpidx.put(proof_idx, Q, s));
-  HIP_OK(dkeys.put(kbytes ? key_blob + k0 : nullptr, kbytes, s));
-  HIP_OK(dkoff.put(koff.data(), Q + 1, s));
-  HIP_OK(dvals.put(vbytes ? val_blob + v0 : nullptr, vbytes, s));
-  HIP_OK(dvoff.put(voff.data(), Q + 1, s));
+  HIP_OK(dkeys.put(keys.len ? key_blob + keys.b0 : nullptr, keys.len, s));
+  HIP_OK(dkoff.put(keys.rebased(), Q + 1, s));
+  HIP_OK(dvals.put(vals.len ? val_blob + vals.b0 : nullptr, vals.len, s));
+  HIP_OK(dvoff.put(vals.rebased(), Q + 1, s));
   HIP_OK(dstatus.alloc(Q));
   HIP_OK(ddig.alloc(N * 32));
-  hipError_t e = pv::launch_sha3_256(dblob.p, dbeg.p, dend.p, N, d.counter.p, w32(ddig.p), d.sha3_blocks, s);
-  if (e == hipSuccess)
-    e = pv::launch_trie_verify(dblob.p, dbeg.p, dend.p, w32(ddig.p), dfirst.p, w32(droots.p), P, dpidx.p, dkeys.p,
-                               dkoff.p, dvals.p, dvoff.p, Q, dstatus.p, merkle_blocks(d), s);
-  if (e == hipSuccess) e = hipMemcpyAsync(status, dstatus.p, Q, hipMemcpyDeviceToHost, s);
-  // the call-scoped buffers must outlive the work queued on s
-  const hipError_t e2 = hipStreamSynchronize(s);
-  HIP_OK(e);
-  HIP_OK(e2);
-  return PV_OK;
+  HIP_OK(pv::launch_sha3_256(dblob.p, dbeg.p, dend.p, N, d.counter.p, w32(ddig.p), d.sha3_blocks, s));
+  HIP_OK(pv::launch_trie_verify(dblob.p, dbeg.p, dend.p, w32(ddig.p), dfirst.p, w32(droots.p), P, dpidx.p, dkeys.p,
+                                dkoff.p, dvals.p, dvoff.p, Q, dstatus.p, merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(status, dstatus.p, Q, hipMemcpyDeviceToHost, s));
+  return tail.finish();
 }
 
 int pv_synth_layout_device(uint32_t cfg, uint32_t mode, uint64_t first, uint64_t n, uint32_t mlen_min,
                            uint32_t mlen_max, uint32_t n_nodes, uint64_t* off, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (!off) return fail(PV_EINVAL, "null device buffer");
   if (mode > PV_SYNTH_COMMIT) return fail(PV_EINVAL, "unknown synth mode %u", mode);
   if (mode == PV_SYNTH_RANGE && mlen_max < mlen_min) return fail(PV_EINVAL, "mlen_max < mlen_min");
   if (mode == PV_SYNTH_COMMIT && (n_nodes == 0 || n_nodes > 1024))
     return fail(PV_EINVAL, "n_nodes must be in 1..1024");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
-  HIP_OK(d->scan.ensure(pv::scan_sums_words(n + 1)));
-  HIP_OK(pv::launch_synth_layout(cfg, mode, first, n, mlen_min, mlen_max, n_nodes, off, d->scan.p, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(en.d->scan.ensure(pv::scan_sums_words(n + 1)));
+  HIP_OK(pv::launch_synth_layout(cfg, mode, first, n, mlen_min, mlen_max, n_nodes, off, en.d->scan.p, en.s));
+  return en.finish();
 }
 
 int pv_synth_fill_device(uint32_t cfg, uint32_t mode, uint64_t first, uint64_t n, uint32_t key_mod,
                          uint32_t n_nodes, const uint64_t* off, uint8_t* blob, uint8_t* seeds, uint8_t* pk,
                          uint8_t* sig, uint8_t* tamper, uint32_t* sender, int device, void* stream) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  DeviceGuard dg;
-  Device* d = find_dev(device);
-  if (!d) return fail(PV_ENOTINIT, "device %d not initialised (call pv_init)", device);
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
   if (!off || !blob || !seeds || !pk || !sig || !tamper) return fail(PV_EINVAL, "null device buffer");
   if (mode > PV_SYNTH_COMMIT) return fail(PV_EINVAL, "unknown synth mode %u", mode);
   if (mode == PV_SYNTH_COMMIT && (n_nodes == 0 || n_nodes > 1024))
     return fail(PV_EINVAL, "n_nodes must be in 1..1024");
-  HIP_OK(hipSetDevice(d->ord));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d->stream;
+  if (const int rc = en.begin(stream)) return rc;
+  hipStream_t s = en.s;
   uint64_t total = 0;
   HIP_OK(hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   HIP_OK(pv::launch_synth(cfg, mode, first, n, key_mod, n_nodes, seeds, tamper, sender, s));
   HIP_OK(pv::launch_synth_fill(cfg, mode, first, n, n_nodes, off, blob, s));
   HIP_OK(hipMemsetAsync(blob + total, 0, 16, s));
-  HIP_OK(pv::launch_sign(seeds, blob, off, n, d->btab.p, pk, sig, s));
+  HIP_OK(pv::launch_sign(seeds, blob, off, n, en.d->btab.p, pk, sig, s));
   HIP_OK(pv::launch_tamper(first, n, tamper, off, blob, sig, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return PV_OK;
+  return en.finish();
 }
 
 int pv_synth_device(uint32_t cfg, uint64_t first, uint64_t n, uint32_t key_mod, uint32_t mlen, uint64_t* off,
