@@ -88,6 +88,33 @@ def build(force=False, verbose=False, defines=(), lib=None):
     return lib
 
 
+DEVCHECK = os.path.join(REPO, 'tools', 'devcheck')
+
+
+def build_devcheck(force=False):
+    """tools/devcheck/libdevcheck.so: the arithmetic primitives as their own device
+    kernels (tests only; the product never links or loads it), with the
+    product's compiler, arch and flags."""
+    lib = os.path.join(DEVCHECK, 'libdevcheck.so')
+    stamp = lib + '.stamp'
+    h = hashlib.sha256(_digest().encode())
+    for fn in sorted(os.listdir(DEVCHECK)):
+        if fn.endswith(('.hip', '.h')):
+            with open(os.path.join(DEVCHECK, fn), 'rb') as fh:
+                h.update(fn.encode() + fh.read())
+    dig = h.hexdigest()
+    if not force and os.path.exists(lib) and os.path.exists(stamp):
+        with open(stamp) as fh:
+            if fh.read().strip() == dig:
+                return lib
+    tmp = lib + '.tmp'
+    _run([HIPCC] + COMMON + ['-x', 'hip', '-shared', os.path.join(DEVCHECK, 'devcheck.hip'), '-o', tmp])
+    os.replace(tmp, lib)
+    with open(stamp, 'w') as fh:
+        fh.write(dig)
+    return lib
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--force', action='store_true')
@@ -97,5 +124,6 @@ if __name__ == '__main__':
     a = ap.parse_args()
     if not a.lib:
         print(build_host(force=a.force))
+        print(build_devcheck(force=a.force))
     print(build(force=a.force, verbose=a.verbose, defines=a.defines, lib=a.lib))
     sys.exit(0)

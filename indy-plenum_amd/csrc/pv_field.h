@@ -650,7 +650,11 @@ PV_HD void fe_neg(fe& h, const fe& f) {
   for (int i = 1; i < 10; ++i) h.v[i] = ((i & 1) ? P2_O : P2_E) - f.v[i];
 }
 
-// one carry pass over 32-bit limbs (inputs up to ~2^31): -> TIGHT
+// one carry pass over 32-bit limbs (inputs up to 2^31 - 1): -> TIGHT, even
+// limbs < 2^26 and odd limbs <= 2^25.  The wrap adds 19 c with c up to 64 to
+// limb 0, which alone would leave it up to 2^26 + 1215 -- past TIGHT's
+// 2^26 + 2^10 once limb 9 reaches 54 * 2^25 -- so it is carried once more into
+// limb 1 (tests/test_devcheck_cases.py runs the all-limbs-2^31-1 case).
 PV_HD void fe_carry(fe& h) {
   PV_COUNT(carry);
   uint32_t c;
@@ -664,6 +668,7 @@ PV_HD void fe_carry(fe& h) {
   c = h.v[7] >> 25; h.v[7] &= M25; h.v[8] += c;
   c = h.v[8] >> 26; h.v[8] &= M26; h.v[9] += c;
   c = h.v[9] >> 25; h.v[9] &= M25; h.v[0] += 19u * c;
+  c = h.v[0] >> 26; h.v[0] &= M26; h.v[1] += c;
 }
 
 // carries out of the EVEN limbs only (into the odd limb above; no wrap):

@@ -314,3 +314,13 @@ void bnc_field(const uint8_t* a32, const uint8_t* b32, uint8_t* prod, uint8_t* s
 }
 
 }  // extern "C"
+
+// Limb-level twins of the device check (tools/devcheck): raw signed limbs in
+// and out, n cases packed one after another, the op bodies the device kernels
+// run (dc_ops_bn.h) on this build's C++ column sums.  bncw_<name>(in, n, out).
+#include "../devcheck/dc_ops_bn.h"
+#define BNC_TWIN(name, IW, OW)                                             \
+  extern "C" void bncw_##name(const uint32_t* in, uint64_t n, uint32_t* out) { \
+    for (uint64_t i = 0; i < n; ++i) dc_op_##name(in + i * IW, out + i * OW); \
+  }
+DC_BN_OPS(BNC_TWIN)

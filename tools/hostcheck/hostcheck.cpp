@@ -437,3 +437,24 @@ void hc_sc_muladd(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t*
 }
 
 }  // extern "C"
+
+// Limb-level twins of the device check (tools/devcheck): the hc_fe_* helpers
+// above take canonical encodings and so only ever see TIGHT operands; these
+// take raw limbs / words, n cases packed one after another, and run the same op
+// bodies as the device kernels (dc_ops_pv.h) through this build's plain C++
+// branches, bound checks on.  hcw_<name>(in, n, out) for every op of
+// DC_LANE_OPS; the quad ops run on the QL = 4 emulation (n = quads).
+#include "../devcheck/dc_ops_pv.h"
+#define HC_LANE_TWIN(name, IW, OW)                                        \
+  extern "C" void hcw_##name(const uint32_t* in, uint64_t n, uint32_t* out) { \
+    for (uint64_t i = 0; i < n; ++i) dc_op_##name(in + i * IW, out + i * OW); \
+  }
+#define HC_QUAD_TWIN(name, IW, OW)                                        \
+  extern "C" void hcw_##name(const uint32_t* in, uint64_t n, uint32_t* out) { \
+    const QRole qr = qrole_of(0);                                         \
+    for (uint64_t i = 0; i < n; ++i) dc_qop_##name(in + i * IW, out + i * OW, qr); \
+  }
+DC_LANE_OPS(HC_LANE_TWIN)
+DC_QUAD_OPS(HC_QUAD_TWIN)
+// (digest 16 words, signature 16 words, force_full) -> 20-word record, status
+extern "C" void hc_lattice_one(const uint32_t* in, uint64_t n, uint32_t* out) { hcw_lattice_one(in, n, out); }
