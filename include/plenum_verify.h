@@ -380,6 +380,86 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
                                  const uint64_t *val_off, uint64_t N, uint64_t P, uint64_t Q, uint8_t *status,
                                  uint8_t *node_digests, int device, void *stream);
 
+/* Resident trie node store: batched state-proof GENERATION, the serving side of the check above.
+ * The reference's trie database is content-addressed and append-only -- a node lives under
+ * sha3(rlp(node)) and never changes (state/trie/pruning_trie.py:346-353) -- and
+ * Trie.generate_state_proof (:1043-1050, :1075-1098; PruningState.generate_state_proof,
+ * state/pruning_state.py:105-106) is Trie._get (:376-407) from a root plus a record of every node
+ * fetched by hash, with the root appended.  So the store only grows, and a proof at any committed
+ * root, current or historical, is a walk over hash lookups.  One call replaces one
+ * generate_state_proof(key, root, serialize=True, get_value=True) per reply of
+ * ReadRequestHandler._get_value_from_state
+ * (plenum/server/request_handlers/handler_interfaces/read_request_handler.py:33-61).
+ *   pv_state_store_create   an empty store on `device` (room for node_hint nodes and byte_hint
+ *                           bytes up front; every buffer doubles on overflow); *store_out > 0
+ *   pv_state_store_add[_device]
+ *       what the host trie's _encode_node (:334-344: _db.inc_refcount(sha3(rlp(node)), rlp(node)))
+ *       adds on commit: n_new node RLPs, node i = node_blob[node_off[i] .. node_off[i+1]) (n_new + 1
+ *       offsets).  The nodes are appended to the store's blob, hashed in place (k_sha3_256) and
+ *       inserted into a digest-keyed hash table.  A node whose digest the store already holds --
+ *       from an earlier call or earlier in this one -- is flagged and gets no second table slot;
+ *       its bytes stay in the blob as dead bytes.  digests (may be NULL; n_new x 32) receives the
+ *       new nodes' SHA3-256; *n_added (may be NULL) the number of nodes new to the store.
+ *       Host form: PV_EINVAL before any launch unless node_off is strictly increasing (an empty
+ *       node is refused).  Device form: DEVICE buffers, not checked; a node whose range is
+ *       empty, reversed or ends past node_off[n_new] is stored as an empty node, which no walk
+ *       reads.  At most 2^32 - 2 nodes are accepted (ids are 32-bit; the table stops at 2^31
+ *       slots, which a store reaches at 2^30 nodes: PV_ENOMEM).
+ *   pv_state_store_info     nodes added, nodes with a table slot (n_nodes - n_unique = duplicates
+ *                           kept as dead bytes), bytes, table slots (a power of two >= 2 n_nodes)
+ *   pv_state_store_free     release it (pv_shutdown releases every store)
+ *   pv_state_store_prove    HOST buffers.  Query q: key q (key_blob / key_off) at root
+ *       roots[root_idx[q]] (32 bytes each; root_idx NULL: root q).  Writes, per query,
+ *         status      PV_SP_OK: the walk ended; val_len == 0 means the key is proven absent.
+ *                     PV_SP_NODE_MISSING: the root or a referenced node is not in the store (the
+ *                     reference's KeyError, which the read handler turns into (None, None)).
+ *                     PV_SP_MALFORMED.  PV_SP_PATH_TOO_LONG: more hashed nodes than max_nodes;
+ *                     node_count is the true count, so the caller can retry.
+ *         node_count  hashed nodes fetched (inline nodes are walked in place and are no proof
+ *                     nodes, as spv_grabbing, pruning_trie.py:233-243, runs only on db fetches, :351-352)
+ *         proof_off   n_queries + 1 offsets into proof_blob; proof q is the serialized proof
+ *                     (Trie.serialize_proof, :1164-1170) of an OK query, empty otherwise
+ *         val_rel, val_len   the value (rlp([v]) as the trie stores it, what get_value=True
+ *                     returns) lies at proof_blob[proof_off[q] + val_rel[q] ..], val_len[q] bytes
+ *       With proof_blob == NULL this is the sizing call: everything but the bytes is written.
+ *       With proof_cap < proof_off[n_queries]: PV_EINVAL before the pack launch, the text names
+ *       both numbers, and proof_off and the per-query outputs are already written.
+ *       PV_EINVAL before any launch: key_off not monotone, root_idx[q] >= n_roots, max_nodes == 0.
+ *   pv_state_store_walk_device / pv_state_store_pack_device
+ *       the two halves with DEVICE buffers, read by the kernels only: the walk writes node_ids
+ *       (n_queries x max_nodes; query q's ids at q * max_nodes, root first) and proof_len; the
+ *       caller scans proof_len into proof_off (n_queries + 1, proof_off[0] = 0) and the pack
+ *       writes proof_blob (proof_off[n_queries] bytes).  A query whose root_idx is >= n_roots
+ *       is PV_SP_MALFORMED; a proof whose ids do not add up to proof_off[q+1] - proof_off[q]
+ *       bytes is not written.
+ * A store's calls are synchronous and ordered on their stream (NULL = the library's).
+ * Two deliberate differences from the reference.  Node order: a proof is the list of the nodes in
+ * REVERSE walk order, terminal node first, root last; root last is the one ordering property
+ * _generate_state_proof has (pf.append(root), and the NOTE at :1102), the rest of the reference's
+ * order is Python set order.  Blank root: the proof is the empty list, the one byte 0xc0, which
+ * is what verify accepts; the reference would serialize [b''].
+ * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal), deletion and
+ * pruning of nodes, building or updating tries on the device. */
+#define PV_SP_PATH_TOO_LONG 4
+int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t *store_out);
+int pv_state_store_add(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
+                       uint8_t *digests, uint64_t *n_added);
+int pv_state_store_add_device(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
+                              uint8_t *digests, void *stream);
+int pv_state_store_info(int32_t store, uint64_t *n_nodes, uint64_t *n_unique, uint64_t *n_bytes, uint64_t *n_slots);
+int pv_state_store_free(int32_t store);
+int pv_state_store_prove(int32_t store, const uint8_t *roots, const uint32_t *root_idx, uint64_t n_roots,
+                         const uint8_t *key_blob, const uint64_t *key_off, uint64_t n_queries, uint32_t max_nodes,
+                         uint8_t *status, uint32_t *node_count, uint64_t *proof_off, uint64_t *val_rel,
+                         uint64_t *val_len, uint8_t *proof_blob, uint64_t proof_cap);
+int pv_state_store_walk_device(int32_t store, const uint8_t *roots, const uint32_t *root_idx, uint64_t n_roots,
+                               const uint8_t *key_blob, const uint64_t *key_off, uint64_t n_queries,
+                               uint32_t max_nodes, uint8_t *status, uint32_t *node_count, uint32_t *node_ids,
+                               uint64_t *proof_len, uint64_t *val_rel, uint64_t *val_len, void *stream);
+int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const uint32_t *node_count,
+                               uint32_t max_nodes, const uint64_t *proof_off, uint64_t n_queries,
+                               uint8_t *proof_blob, void *stream);
+
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of
  *                 batch b = node 32 w + j cast a valid vote in batch b (a voter SET:

@@ -26,6 +26,7 @@
 #include "../../include/plenum_verify.h"
 #include "pv_kernels.h"
 #include "pv_trie_proof.h"
+#include "pv_trie_store.h"
 
 static_assert(pv::SP_OK == PV_SP_OK && pv::SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
                   pv::SP_NODE_MISSING == PV_SP_NODE_MISSING && pv::SP_MALFORMED == PV_SP_MALFORMED,
@@ -545,6 +546,7 @@ struct DeviceGuard {
 std::mutex g_mu;
 std::vector<Device> g_devs;
 void release_trees();   // resident Merkle trees (pv_merkle_tree_*), below
+void release_stores();  // resident trie node stores (pv_state_store_*), below
 
 Device* find_dev(int id) {
   for (auto& d : g_devs)
@@ -1649,6 +1651,7 @@ void pv_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_mu);
   DeviceGuard dg;
   release_trees();
+  release_stores();
   for (auto& d : g_devs) release_device(d);
   g_devs.clear();
   g_kc.clear();
@@ -2805,3 +2808,362 @@ int pv_synth_device(uint32_t cfg, uint64_t first, uint64_t n, uint32_t key_mod, 
 }
 
 }  // extern "C"
+
+// --------------------------------- resident trie node store / proof generation
+namespace {
+
+// A resident node store (pv_trie_store.h): the nodes' bytes, ranges, digests
+// and duplicate flags, the digest-keyed table and the device count of nodes
+// that hold a table slot.  Every buffer doubles on overflow with a
+// device-to-device copy on the call's stream, as the resident Merkle tree does.
+struct StateStore {
+  bool live = false;
+  int dev = -1;              // Device::id
+  uint64_t n_nodes = 0, n_unique = 0, n_bytes = 0;
+  uint32_t slots = 0;
+  uint8_t* blob = nullptr;   // cap_bytes + 16 bytes
+  uint64_t cap_bytes = 0;
+  uint64_t *beg = nullptr, *end = nullptr;   // cap_nodes each
+  uint32_t* dig = nullptr;                   // cap_nodes x 8 words
+  uint8_t* dup = nullptr;                    // cap_nodes
+  uint64_t cap_nodes = 0;
+  uint32_t* table = nullptr;                 // slots
+  unsigned int* unique = nullptr;            // device copy of n_unique (k_trie_store_insert adds to it)
+};
+std::vector<StateStore> g_stores;   // store id = index + 1
+
+void store_release(StateStore& st) {
+  if (!st.live) return;
+  if (Device* d = find_dev(st.dev)) {
+    (void)hipSetDevice(d->ord);
+    (void)hipStreamSynchronize(d->stream);
+  }
+  void* bufs[] = {st.blob, st.beg, st.end, st.dig, st.dup, st.table, st.unique};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  st = StateStore();
+}
+
+StateStore* find_store(int32_t id) {
+  if (id < 1 || (size_t)id > g_stores.size() || !g_stores[id - 1].live) return nullptr;
+  return &g_stores[id - 1];
+}
+
+// resolve a store id and point the entry scope at the store's device
+int store_enter(Entry& en, int32_t id, StateStore** st) {
+  if (const int rc = en.check()) return rc;
+  *st = find_store(id);
+  if (!*st) return fail(PV_EINVAL, "no state store with id %d", (int)id);
+  en.d = find_dev((*st)->dev);
+  if (!en.d) return fail(PV_EINVAL, "the device of state store %d is gone", (int)id);
+  return PV_OK;
+}
+
+// *p holds at least `need` elements afterwards (+ `pad` elements never counted
+// in the capacity); the `used` elements in use move device-to-device on s
+template <typename T>
+int store_grow(T** p, uint64_t* cap, uint64_t need, uint64_t used, uint64_t pad, hipStream_t s) {
+  if (*p && need <= *cap) return PV_OK;
+  uint64_t nc = *cap ? *cap : 1;
+  while (nc < need) nc *= 2;
+  T* np = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void**>(&np), (nc + pad) * sizeof(T)));
+  if (*p) {
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(np, *p, used * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipFree(np);
+      HIP_OK(e);
+    }
+    (void)hipFree(*p);
+  }
+  *p = np;
+  *cap = nc;
+  return PV_OK;
+}
+
+int store_reserve(StateStore& st, uint64_t nodes, uint64_t bytes, hipStream_t s) {
+  if (const int rc = store_grow(&st.blob, &st.cap_bytes, bytes, st.n_bytes, 16, s)) return rc;
+  if (nodes <= st.cap_nodes && st.beg) return PV_OK;
+  // the four per-node arrays grow in step: same start, same doubling
+  uint64_t c0 = st.cap_nodes, c1 = st.cap_nodes, c2 = st.cap_nodes, cd = st.cap_nodes * 8;
+  if (const int rc = store_grow(&st.beg, &c0, nodes, st.n_nodes, 0, s)) return rc;
+  if (const int rc = store_grow(&st.end, &c1, nodes, st.n_nodes, 0, s)) return rc;
+  if (const int rc = store_grow(&st.dup, &c2, nodes, st.n_nodes, 0, s)) return rc;
+  if (const int rc = store_grow(&st.dig, &cd, c0 * 8, st.n_nodes * 8, 0, s)) return rc;
+  st.cap_nodes = c0;
+  return PV_OK;
+}
+
+// a table of `slots` slots holding every node that has one; launched before an
+// insert that would push the nodes above slots / 2
+int store_rehash(StateStore& st, uint32_t slots, const Device& d, hipStream_t s) {
+  uint32_t* nt = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void**>(&nt), (size_t)slots * 4));
+  hipError_t e = hipMemsetAsync(nt, 0, (size_t)slots * 4, s);
+  if (e == hipSuccess)
+    e = pv::launch_trie_store_rehash(nt, slots, st.dig, st.dup, (uint32_t)st.n_nodes, merkle_blocks(d), s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    (void)hipFree(nt);
+    HIP_OK(e);
+  }
+  if (st.table) (void)hipFree(st.table);
+  st.table = nt;
+  st.slots = slots;
+  return PV_OK;
+}
+
+// pv_state_store_add[_device]: host = the arrays are host memory and checked here
+int store_add(int32_t id, const uint8_t* node_blob, const uint64_t* node_off, uint64_t n_new, uint8_t* digests,
+              uint64_t* n_added, bool host, void* stream) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, id, &st)) return rc;
+  if (n_added) *n_added = 0;
+  if (n_new == 0) return PV_OK;
+  if (!node_blob || !node_off) return fail(PV_EINVAL, host ? "null buffer" : "null device buffer");
+  if (n_new > pv::TS_MAX_NODES || st->n_nodes + n_new > pv::TS_MAX_NODES)
+    return fail(PV_EINVAL, "state store limited to 2^32 - 2 nodes");
+  if (host)
+    for (uint64_t i = 0; i < n_new; ++i)
+      if (node_off[i + 1] <= node_off[i])
+        return fail(PV_EINVAL, "node_off not strictly increasing at %llu (an empty node)", (unsigned long long)i);
+  if (const int rc = en.begin(stream)) return rc;
+  Device& d = *en.d;
+  hipStream_t s = en.s;
+  uint64_t ends[2] = {0, 0};   // node_off[0], node_off[n_new]
+  if (host) {
+    ends[0] = node_off[0];
+    ends[1] = node_off[n_new];
+  } else {   // the two ends size the copy; the offsets between them are read by the kernel only
+    HIP_OK(hipMemcpyAsync(&ends[0], node_off, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(&ends[1], node_off + n_new, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (ends[1] < ends[0]) return fail(PV_EINVAL, "node_off ends below its start");
+  }
+  const uint64_t total = ends[1] - ends[0];
+  if (total > (1ull << 40)) return fail(PV_EINVAL, "more than 2^40 bytes of nodes in one call");
+  const uint64_t nodes = st->n_nodes + n_new;
+  if (const int rc = store_reserve(*st, nodes, st->n_bytes + total, s)) return rc;
+  TmpBuf<uint64_t> doff;
+  StreamDrain tail{s};
+  const uint64_t* poff = node_off;
+  if (host) {
+    HIP_OK(doff.put(node_off, n_new + 1, s));
+    poff = doff.p;
+  }
+  if (total)
+    HIP_OK(hipMemcpyAsync(st->blob + st->n_bytes, node_blob + ends[0], total,
+                          host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(st->blob + st->n_bytes + total, 0, 16, s));
+  HIP_OK(hipMemsetAsync(st->dup + st->n_nodes, 0, n_new, s));
+  HIP_OK(pv::launch_trie_store_layout(poff, n_new, st->n_bytes, total, st->beg, st->end, st->n_nodes,
+                                      merkle_blocks(d), s));
+  HIP_OK(pv::launch_sha3_256(st->blob, st->beg + st->n_nodes, st->end + st->n_nodes, n_new, d.counter.p,
+                             st->dig + 8 * st->n_nodes, d.sha3_blocks, s));
+  if (nodes > st->slots / 2) {
+    uint64_t ns = st->slots;
+    while (nodes > ns / 2) ns *= 2;   // nodes < 2^32, so ns <= 2^33
+    if (ns > (1ull << 31)) return fail(PV_ENOMEM, "state store table above 2^31 slots");
+    if (const int rc = store_rehash(*st, (uint32_t)ns, d, s)) return rc;
+  }
+  HIP_OK(pv::launch_trie_store_insert(st->table, st->slots, st->dig, st->dup, (uint32_t)st->n_nodes, (uint32_t)n_new,
+                                      st->unique, merkle_blocks(d), s));
+  unsigned int uniq = 0;
+  HIP_OK(hipMemcpyAsync(&uniq, st->unique, 4, hipMemcpyDeviceToHost, s));
+  if (digests)
+    HIP_OK(hipMemcpyAsync(digests, st->dig + 8 * st->n_nodes, n_new * 32,
+                          host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+  if (const int rc = tail.finish()) return rc;
+  if (n_added) *n_added = uniq - st->n_unique;
+  st->n_unique = uniq;
+  st->n_nodes = nodes;
+  st->n_bytes += total;
+  return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t* store_out) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (!store_out) return fail(PV_EINVAL, "null pointer");
+  if (node_hint > pv::TS_MAX_NODES) return fail(PV_EINVAL, "node_hint above 2^32 - 2 nodes");
+  if (byte_hint > (1ull << 40)) return fail(PV_EINVAL, "byte_hint above 2^40 bytes");
+  size_t idx = 0;
+  while (idx < g_stores.size() && g_stores[idx].live) ++idx;
+  if (idx == g_stores.size()) {
+    if (g_stores.size() >= 0x7fffffffull) return fail(PV_ENOMEM, "too many state stores");
+    g_stores.emplace_back();
+  }
+  StateStore& st = g_stores[idx];
+  st = StateStore();
+  st.live = true;
+  st.dev = en.d->id;
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
+  uint64_t slots = pv::TS_MIN_SLOTS;
+  while (node_hint > slots / 2) slots *= 2;
+  int rc = slots > (1ull << 31) ? fail(PV_ENOMEM, "state store table above 2^31 slots") : PV_OK;
+  if (rc == PV_OK) rc = store_reserve(st, node_hint ? node_hint : 1, byte_hint ? byte_hint : 1, s);
+  if (rc == PV_OK) rc = store_rehash(st, (uint32_t)slots, *en.d, s);   // an empty table
+  if (rc == PV_OK) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&st.unique), 4);
+    if (e == hipSuccess) e = hipMemsetAsync(st.unique, 0, 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(st.blob, 0, 16, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) rc = fail(PV_EIO, "state store allocation failed: %s", hipGetErrorString(e));
+  }
+  if (rc) {
+    store_release(st);
+    return rc;
+  }
+  *store_out = (int32_t)(idx + 1);
+  return PV_OK;
+}
+
+int pv_state_store_free(int32_t store) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  DeviceGuard dg;
+  StateStore* st = find_store(store);
+  if (!st) return fail(PV_EINVAL, "no state store with id %d", (int)store);
+  store_release(*st);
+  return PV_OK;
+}
+
+int pv_state_store_add(int32_t store, const uint8_t* node_blob, const uint64_t* node_off, uint64_t n_new,
+                       uint8_t* digests, uint64_t* n_added) {
+  return store_add(store, node_blob, node_off, n_new, digests, n_added, true, nullptr);
+}
+
+int pv_state_store_add_device(int32_t store, const uint8_t* node_blob, const uint64_t* node_off, uint64_t n_new,
+                              uint8_t* digests, void* stream) {
+  return store_add(store, node_blob, node_off, n_new, digests, nullptr, false, stream);
+}
+
+int pv_state_store_info(int32_t store, uint64_t* n_nodes, uint64_t* n_unique, uint64_t* n_bytes, uint64_t* n_slots) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_nodes) *n_nodes = st->n_nodes;
+  if (n_unique) *n_unique = st->n_unique;
+  if (n_bytes) *n_bytes = st->n_bytes;
+  if (n_slots) *n_slots = st->slots;
+  return PV_OK;
+}
+
+int pv_state_store_walk_device(int32_t store, const uint8_t* roots, const uint32_t* root_idx, uint64_t n_roots,
+                               const uint8_t* key_blob, const uint64_t* key_off, uint64_t n_queries,
+                               uint32_t max_nodes, uint8_t* status, uint32_t* node_count, uint32_t* node_ids,
+                               uint64_t* proof_len, uint64_t* val_rel, uint64_t* val_len, void* stream) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_queries == 0) return PV_OK;
+  if (!roots || !key_blob || !key_off || !status || !node_count || !node_ids || !proof_len || !val_rel || !val_len)
+    return fail(PV_EINVAL, "null device buffer");
+  if (max_nodes == 0) return fail(PV_EINVAL, "max_nodes must be >= 1");
+  if (n_roots == 0) return fail(PV_EINVAL, "queries without roots");
+  if (n_queries > (1ull << 40) / max_nodes) return fail(PV_EINVAL, "n_queries x max_nodes above 2^40 node ids");
+  if (reinterpret_cast<uintptr_t>(roots) & 3u) return fail(PV_EINVAL, "roots must be 4-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_trie_prove(st->blob, st->beg, st->end, st->dig, st->table, st->slots, (uint32_t)st->n_nodes,
+                               w32(roots), root_idx, n_roots, key_blob, key_off, n_queries, max_nodes, status,
+                               node_count, node_ids, proof_len, val_rel, val_len, merkle_blocks(*en.d), en.s));
+  return en.finish();
+}
+
+int pv_state_store_pack_device(int32_t store, const uint32_t* node_ids, const uint32_t* node_count,
+                               uint32_t max_nodes, const uint64_t* proof_off, uint64_t n_queries,
+                               uint8_t* proof_blob, void* stream) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_queries == 0) return PV_OK;
+  if (!node_ids || !node_count || !proof_off || !proof_blob) return fail(PV_EINVAL, "null device buffer");
+  if (max_nodes == 0) return fail(PV_EINVAL, "max_nodes must be >= 1");
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(pv::launch_trie_proof_pack(st->blob, st->beg, st->end, (uint32_t)st->n_nodes, node_ids, node_count,
+                                    max_nodes, proof_off, n_queries, proof_blob, merkle_blocks(*en.d), en.s));
+  return en.finish();
+}
+
+int pv_state_store_prove(int32_t store, const uint8_t* roots, const uint32_t* root_idx, uint64_t n_roots,
+                         const uint8_t* key_blob, const uint64_t* key_off, uint64_t n_queries, uint32_t max_nodes,
+                         uint8_t* status, uint32_t* node_count, uint64_t* proof_off, uint64_t* val_rel,
+                         uint64_t* val_len, uint8_t* proof_blob, uint64_t proof_cap) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_queries == 0) return PV_OK;
+  if (!roots || !key_off || !status || !node_count || !proof_off || !val_rel || !val_len)
+    return fail(PV_EINVAL, "null buffer");
+  if (max_nodes == 0) return fail(PV_EINVAL, "max_nodes must be >= 1");
+  if (n_roots == 0) return fail(PV_EINVAL, "queries without roots");
+  if (n_queries > (1ull << 40) / max_nodes) return fail(PV_EINVAL, "n_queries x max_nodes above 2^40 node ids");
+  if (!root_idx && n_roots < n_queries)
+    return fail(PV_EINVAL, "%llu roots for %llu queries without root_idx", (unsigned long long)n_roots,
+                (unsigned long long)n_queries);
+  Ragged keys(key_off, n_queries);
+  if (const int rc = keys.check("key_off")) return rc;
+  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
+  if (root_idx)
+    for (uint64_t i = 0; i < n_queries; ++i)
+      if (root_idx[i] >= n_roots)
+        return fail(PV_EINVAL, "root_idx[%llu] = %u is not below n_roots %llu", (unsigned long long)i, root_idx[i],
+                    (unsigned long long)n_roots);
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> droots, dkeys, dstatus, dproof;
+  TmpBuf<uint32_t> dridx, dcount, dids;
+  TmpBuf<uint64_t> dkoff, dlen, dvrel, dvlen, dpoff;
+  StreamDrain tail{s};
+  HIP_OK(droots.put(roots, n_roots * 32, s));
+  if (root_idx) HIP_OK(dridx.put(root_idx, n_queries, s));
+  HIP_OK(dkeys.alloc(keys.len + 4));
+  if (keys.len) HIP_OK(hipMemcpyAsync(dkeys.p, key_blob + keys.b0, keys.len, hipMemcpyHostToDevice, s));
+  HIP_OK(dkoff.put(keys.rebased(), n_queries + 1, s));
+  HIP_OK(dstatus.alloc(n_queries));
+  HIP_OK(dcount.alloc(n_queries));
+  HIP_OK(dids.alloc(n_queries * max_nodes));
+  HIP_OK(dlen.alloc(n_queries));
+  HIP_OK(dvrel.alloc(n_queries));
+  HIP_OK(dvlen.alloc(n_queries));
+  HIP_OK(pv::launch_trie_prove(st->blob, st->beg, st->end, st->dig, st->table, st->slots, (uint32_t)st->n_nodes,
+                               w32(droots.p), root_idx ? dridx.p : nullptr, n_roots, dkeys.p, dkoff.p, n_queries,
+                               max_nodes, dstatus.p, dcount.p, dids.p, dlen.p, dvrel.p, dvlen.p, merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(status, dstatus.p, n_queries, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(node_count, dcount.p, n_queries * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(proof_off + 1, dlen.p, n_queries * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(val_rel, dvrel.p, n_queries * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(val_len, dvlen.p, n_queries * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  proof_off[0] = 0;   // the lengths, scanned in place
+  for (uint64_t i = 0; i < n_queries; ++i) proof_off[i + 1] += proof_off[i];
+  const uint64_t total = proof_off[n_queries];
+  if (!proof_blob) return tail.finish();   // the sizing call
+  if (proof_cap < total)
+    return fail(PV_EINVAL, "proof_cap %llu is below the %llu bytes of the proofs", (unsigned long long)proof_cap,
+                (unsigned long long)total);
+  if (total == 0) return tail.finish();
+  HIP_OK(dpoff.put(proof_off, n_queries + 1, s));
+  HIP_OK(dproof.alloc(total));
+  HIP_OK(pv::launch_trie_proof_pack(st->blob, st->beg, st->end, (uint32_t)st->n_nodes, dids.p, dcount.p, max_nodes,
+                                    dpoff.p, n_queries, dproof.p, merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(proof_blob, dproof.p, total, hipMemcpyDeviceToHost, s));
+  return tail.finish();
+}
+
+}  // extern "C"
+
+namespace {
+void release_stores() {
+  for (auto& st : g_stores) store_release(st);
+  g_stores.clear();
+}
+}  // namespace

@@ -199,6 +199,37 @@ hipError_t launch_trie_verify(const uint8_t* node_blob, const uint64_t* node_beg
                               const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off, uint64_t n,
                               uint8_t* status, int max_blocks, hipStream_t s);
 
+// Resident trie node store and state-proof generation (pv_trie_store.h); all device memory.
+//   trie_store_layout  node first + i = blob[base + (node_off[i] - node_off[0]) ..
+//                      base + (node_off[i + 1] - node_off[0])); a range that is empty, reversed or
+//                      ends past `total` becomes the empty range at base (never read, walks as
+//                      malformed)
+//   trie_store_insert  one lane per new node id first .. first + n_new - 1 (hashed already);
+//                      *unique += the nodes whose digest the table did not hold; dup[] flags the rest
+//   trie_store_rehash  ids 0 .. n - 1 that are not flagged, into an empty table
+//   trie_prove         one query per lane: root roots[root_idx ? root_idx[q] : q], key q ->
+//                      status, node_count, node_ids[q * max_nodes ..], proof_len, val_rel, val_len
+//   trie_proof_pack    one wave per proof: list header at proof_off[q], then the nodes' bytes in
+//                      reverse walk order; a proof whose ids do not add up to
+//                      proof_off[q + 1] - proof_off[q] bytes is not written
+hipError_t launch_trie_store_layout(const uint64_t* node_off, uint64_t n_new, uint64_t base, uint64_t total,
+                                    uint64_t* beg, uint64_t* end, uint64_t first, int max_blocks, hipStream_t s);
+hipError_t launch_trie_store_insert(uint32_t* table, uint32_t slots, const uint32_t* dig, uint8_t* dup,
+                                    uint32_t first, uint32_t n_new, unsigned int* unique, int max_blocks,
+                                    hipStream_t s);
+hipError_t launch_trie_store_rehash(uint32_t* table, uint32_t slots, const uint32_t* dig, uint8_t* dup, uint32_t n,
+                                    int max_blocks, hipStream_t s);
+hipError_t launch_trie_prove(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                             const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t* roots,
+                             const uint32_t* root_idx, uint64_t n_roots, const uint8_t* key_blob,
+                             const uint64_t* key_off, uint64_t n_queries, uint32_t max_nodes, uint8_t* status,
+                             uint32_t* node_count, uint32_t* node_ids, uint64_t* proof_len, uint64_t* val_rel,
+                             uint64_t* val_len, int max_blocks, hipStream_t s);
+hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, uint32_t n_nodes,
+                                  const uint32_t* node_ids, const uint32_t* node_count, uint32_t max_nodes,
+                                  const uint64_t* proof_off, uint64_t n_queries, uint8_t* proof_blob, int max_blocks,
+                                  hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

@@ -18,6 +18,7 @@
 #include "pv_merkle_proof.h"
 #include "pv_sha3.h"
 #include "pv_trie_proof.h"
+#include "pv_trie_store.h"
 #include "pv_kernels.h"
 #include "plenum_verify.h"
 
@@ -1786,6 +1787,147 @@ hipError_t launch_trie_verify(const uint8_t* node_blob, const uint64_t* node_beg
   hipLaunchKernelGGL(k_trie_verify, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, node_blob, node_beg, node_end,
                      node_dig, proof_first, roots, n_proofs, proof_idx, key_blob, key_off, val_blob, val_off, n,
                      status);
+  return hipGetLastError();
+}
+
+// ------------------------------ resident trie node store / proof generation
+// pv_trie_store.h.  The nodes' byte ranges, from the caller's ragged offsets.
+static_assert(SP_PATH_TOO_LONG == PV_SP_PATH_TOO_LONG, "public state-proof status codes");
+__global__ __launch_bounds__(256) void k_trie_store_layout(const uint64_t* __restrict__ node_off, uint64_t n_new,
+                                                            uint64_t base, uint64_t total,
+                                                            uint64_t* __restrict__ beg, uint64_t* __restrict__ end,
+                                                            uint64_t first) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  const uint64_t o0 = node_off[0];
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_new; i += stride) {
+    const uint64_t a = node_off[i] - o0, b = node_off[i + 1] - o0;
+    const bool ok = a < b && b <= total;
+    beg[first + i] = base + (ok ? a : 0);
+    end[first + i] = base + (ok ? b : 0);
+  }
+}
+
+// One lane per new node, after k_sha3_256 has hashed the new nodes in place.
+__global__ __launch_bounds__(256) void k_trie_store_insert(uint32_t* __restrict__ table, uint32_t slots,
+                                                            const uint32_t* __restrict__ dig,
+                                                            uint8_t* __restrict__ dup, uint32_t first,
+                                                            uint32_t n_new, unsigned int* __restrict__ unique) {
+  const uint32_t stride = gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_new; i += stride)
+    if (ts_insert(table, slots, dig, dup, first + (uint32_t)i)) atomicAdd(unique, 1u);
+}
+
+// Every id that holds a table slot, into an empty table of another size.
+__global__ __launch_bounds__(256) void k_trie_store_rehash(uint32_t* __restrict__ table, uint32_t slots,
+                                                            const uint32_t* __restrict__ dig,
+                                                            uint8_t* __restrict__ dup, uint32_t n) {
+  const uint32_t stride = gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+    if (!dup[i]) (void)ts_insert(table, slots, dig, dup, (uint32_t)i);
+}
+
+// One query per lane; lanes of a wave diverge in trip count only.
+__global__ __launch_bounds__(256) void k_trie_prove(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ beg, const uint64_t* __restrict__ end,
+    const uint32_t* __restrict__ dig, const uint32_t* __restrict__ table, uint32_t slots, uint32_t n_nodes,
+    const uint32_t* __restrict__ roots, const uint32_t* __restrict__ root_idx, uint64_t n_roots,
+    const uint8_t* __restrict__ key_blob, const uint64_t* __restrict__ key_off, uint64_t n, uint32_t max_nodes,
+    uint8_t* __restrict__ status, uint32_t* __restrict__ node_count, uint32_t* __restrict__ node_ids,
+    uint64_t* __restrict__ proof_len, uint64_t* __restrict__ val_rel, uint64_t* __restrict__ val_len) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const uint64_t p = root_idx ? root_idx[i] : i;
+    SgResult r;
+    r.status = SP_MALFORMED;
+    r.node_count = 0;
+    r.body_len = r.last_beg = r.val_beg = r.val_len = 0;
+    if (p < n_roots) {
+      uint32_t rt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) rt[k] = roots[8 * p + k];
+      const uint64_t ko = key_off[i];
+      sg_walk(blob, beg, end, dig, table, slots, n_nodes, rt, key_blob + ko, key_off[i + 1] - ko,
+              node_ids + i * max_nodes, max_nodes, r);
+    }
+    uint64_t pl, vr, vl;
+    sg_outputs(r, pl, vr, vl);
+    status[i] = (uint8_t)r.status;
+    node_count[i] = r.node_count;
+    proof_len[i] = pl;
+    val_rel[i] = vr;
+    val_len[i] = vl;
+  }
+}
+
+// One wave per proof; lanes stride over the bytes of each node.
+__global__ __launch_bounds__(256) void k_trie_proof_pack(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ beg, const uint64_t* __restrict__ end,
+    uint32_t n_nodes, const uint32_t* __restrict__ node_ids, const uint32_t* __restrict__ node_count,
+    uint32_t max_nodes, const uint64_t* __restrict__ proof_off, uint64_t n, uint8_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t q = wave; q < n; q += waves) {
+    const uint64_t o = proof_off[q], e = proof_off[q + 1];
+    const uint32_t* ids = node_ids + q * max_nodes;
+    const uint32_t count = node_count[q];
+    uint64_t body;
+    if (e <= o || !sg_pack_check(beg, end, n_nodes, ids, count, max_nodes, e - o, body)) continue;
+    const uint32_t hl = rlp_list_header_len(body);
+    if (lane < hl) out[o + lane] = rlp_list_header_byte(body, hl, lane);
+    uint64_t w = o + hl;
+    for (uint32_t k = count; k-- > 0;) {
+      const uint32_t id = ids[k];
+      const uint64_t b = beg[id], len = end[id] - b;
+      for (uint64_t x = lane; x < len; x += 64) out[w + x] = blob[b + x];
+      w += len;
+    }
+  }
+}
+
+hipError_t launch_trie_store_layout(const uint64_t* node_off, uint64_t n_new, uint64_t base, uint64_t total,
+                                    uint64_t* beg, uint64_t* end, uint64_t first, int max_blocks, hipStream_t s) {
+  if (n_new == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_store_layout, dim3(mp_grid(n_new, max_blocks)), dim3(256), 0, s, node_off, n_new, base,
+                     total, beg, end, first);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_store_insert(uint32_t* table, uint32_t slots, const uint32_t* dig, uint8_t* dup,
+                                    uint32_t first, uint32_t n_new, unsigned int* unique, int max_blocks,
+                                    hipStream_t s) {
+  if (n_new == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_store_insert, dim3(mp_grid(n_new, max_blocks)), dim3(256), 0, s, table, slots, dig, dup,
+                     first, n_new, unique);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_store_rehash(uint32_t* table, uint32_t slots, const uint32_t* dig, uint8_t* dup, uint32_t n,
+                                    int max_blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_store_rehash, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, table, slots, dig, dup, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_prove(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                             const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t* roots,
+                             const uint32_t* root_idx, uint64_t n_roots, const uint8_t* key_blob,
+                             const uint64_t* key_off, uint64_t n_queries, uint32_t max_nodes, uint8_t* status,
+                             uint32_t* node_count, uint32_t* node_ids, uint64_t* proof_len, uint64_t* val_rel,
+                             uint64_t* val_len, int max_blocks, hipStream_t s) {
+  if (n_queries == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_prove, dim3(mp_grid(n_queries, max_blocks)), dim3(256), 0, s, blob, beg, end, dig, table,
+                     slots, n_nodes, roots, root_idx, n_roots, key_blob, key_off, n_queries, max_nodes, status,
+                     node_count, node_ids, proof_len, val_rel, val_len);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, uint32_t n_nodes,
+                                  const uint32_t* node_ids, const uint32_t* node_count, uint32_t max_nodes,
+                                  const uint64_t* proof_off, uint64_t n_queries, uint8_t* proof_blob, int max_blocks,
+                                  hipStream_t s) {
+  if (n_queries == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_proof_pack, dim3(mp_grid(n_queries * 64, max_blocks)), dim3(256), 0, s, blob, beg,
+                     end, n_nodes, node_ids, node_count, max_nodes, proof_off, n_queries, proof_blob);
   return hipGetLastError();
 }
 

@@ -19,6 +19,9 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
                   ledger/merkle_verifier.py, ledger/compact_merkle_tree.py
   state_proofs    GpuStateVerifier (+ verify_state_proofs_batch), sha3_256_batch
                   state/pruning_state.py, state/trie/pruning_trie.py
+  state_store     GpuStateStore: a device-resident trie node store,
+                  generate_state_proof (+ generate_state_proofs_batch)
+                  state/pruning_state.py, state/trie/pruning_trie.py
   serialization, base58, exceptions, constants   the data formats either side
 
 device.py holds the device-resident (torch tensor) entry points; _native.py is
@@ -29,7 +32,8 @@ __version__ = '0.1.0'
 # exported from merkle_proofs, imported on first use (the package import stays light)
 _MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
 _STATE_PROOFS = ('GpuStateVerifier', 'verify_state_proofs_batch', 'sha3_256_batch')
-__all__ = list(_MERKLE_PROOFS + _STATE_PROOFS)
+_STATE_STORE = ('GpuStateStore',)
+__all__ = list(_MERKLE_PROOFS + _STATE_PROOFS + _STATE_STORE)
 
 
 def __getattr__(name):
@@ -39,4 +43,7 @@ def __getattr__(name):
     if name in _STATE_PROOFS:
         from . import state_proofs
         return getattr(state_proofs, name)
+    if name in _STATE_STORE:
+        from . import state_store
+        return getattr(state_store, name)
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -100,6 +100,21 @@ SIGNATURES = [
     ('pv_state_proof_verify_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
       ctypes.c_int, _vp]),
+    ('pv_state_store_create', ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    ('pv_state_store_add', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_uint64)]),
+    ('pv_state_store_add_device', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    ('pv_state_store_info', ctypes.c_int, [ctypes.c_int32] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
+    ('pv_state_store_free', ctypes.c_int, [ctypes.c_int32]),
+    ('pv_state_store_prove', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+      _vp, ctypes.c_uint64]),
+    ('pv_state_store_walk_device', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+      _vp, _vp]),
+    ('pv_state_store_pack_device', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_verify_keyed_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_int, _vp]),
     ('pv_time_verify_keyed_device', ctypes.c_int,

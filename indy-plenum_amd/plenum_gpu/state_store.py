@@ -1,0 +1,338 @@
+"""Resident trie node store: batched state-proof generation on the GPU.
+
+The serving side of state_proofs.py.  A node answers every GET_* with
+ReadRequestHandler._get_value_from_state
+(plenum/server/request_handlers/handler_interfaces/read_request_handler.py:33-61):
+one `generate_state_proof(key, root, serialize=True, get_value=True)` per reply.
+The reference's trie database is content-addressed and append-only -- a node is
+stored under sha3(rlp(node)) and never changes (state/trie/pruning_trie.py:346-353)
+-- and generate_state_proof (:1043-1050, :1075-1098) is Trie._get from a root plus
+a record of every node fetched by hash, with the root appended.  So nothing has to
+be mutable on the device: `GpuStateStore` grows by "add these node RLPs", which the
+host trie hands over on commit, and a proof at any committed root, current or
+historical, is a walk over hash lookups.  A batch of replies is one call.
+
+* `GpuStateStore.add_nodes(node RLPs)` -- pv_state_store_add: the nodes are appended
+  to a device blob, hashed in place (k_sha3_256) and inserted into a digest-keyed hash
+  table (k_trie_store_insert).
+* `generate_state_proofs_batch([(root, key), ...])` -- pv_state_store_prove: one lane
+  per query walks from its root (k_trie_prove), one wave per proof gathers the
+  serialized bytes (k_trie_proof_pack).
+* `generate_state_proof(key, root, serialize, get_value)` has PruningState's signature
+  (state/pruning_state.py:105-106).
+* `walk_host(db, root, key)` is the pure-Python mirror of sg_walk (csrc/pv_trie_store.h)
+  plus the serialization: the statement of the algorithm, used by the CPU tests.
+
+There is no CPU path here: the store lives on the device, and a missing library or
+GPU raises.
+
+Two deliberate differences from the reference.  Node order: a proof lists the hashed
+nodes of the walk in reverse, terminal node first, root last.  Root last is the one
+ordering property _generate_state_proof has (pf.append(root), and the NOTE at :1102);
+the rest of the reference's order is Python set order.  Blank root: the proof is the
+empty list (serialized: the one byte 0xc0), which is what the verifier accepts; the
+reference would return [b''].
+
+Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal),
+deletion and pruning of nodes, building or updating tries on the device.
+"""
+import ctypes
+import hashlib
+
+import numpy as np
+
+from . import _native as nat
+from .state_proofs import (BLANK_NODE, BLANK_ROOT, PV_SP_MALFORMED, PV_SP_NODE_MISSING, PV_SP_OK, _length_prefix,
+                           _nibble, _p, _rlp_item, rlp_encode, rlp_split_list)
+
+PV_SP_PATH_TOO_LONG = 4   # include/plenum_verify.h
+
+
+def rlp_decode(data):
+    """one RLP item -> bytes or nested lists (lengths as state/util/fast_rlp.py:47-71,
+    each checked against the enclosing end); ValueError when it overruns or bytes are left"""
+    data = bytes(data)
+
+    def item(pos, lim):
+        it = _rlp_item(data, pos, lim)
+        if it is None:
+            raise ValueError('RLP item overruns its enclosing item')
+        is_list, pb, pe = it
+        if not is_list:
+            return data[pb:pe], pe
+        out = []
+        while pb < pe:
+            x, pb = item(pb, pe)
+            out.append(x)
+        return out, pe
+    x, end = item(0, len(data))
+    if end != len(data):
+        raise ValueError('bytes after the RLP item')
+    return x
+
+
+def serialize_nodes(nodes):
+    """rlp(list of nodes) from the nodes' own RLP, walk order in, reverse order out"""
+    body = b''.join(reversed(nodes))
+    return _length_prefix(len(body), 192) + body
+
+
+def walk_host(db, root, key, max_nodes=None):
+    """sg_walk of csrc/pv_trie_store.h in Python over `db` = {sha3(node RLP): node RLP}.
+
+    -> (status, nodes, value, proof, val_rel): the RLP of every node fetched by hash in
+    walk order (root first; inline nodes are walked in place and are not among them), the
+    value as the trie stores it (b'' = proven absent), the serialized proof (reverse walk
+    order; None unless status is PV_SP_OK) and the value's offset in it (the value lies in
+    the terminal node, which is serialized first).  With max_nodes, a walk of more hashed
+    nodes is PV_SP_PATH_TOO_LONG and `nodes` holds all of them (the true count)."""
+    root, key = bytes(root), bytes(key)
+    if root == BLANK_ROOT:
+        return PV_SP_OK, [], b'', b'\xc0', 0
+    blob = db.get(root)
+    if blob is None:
+        return PV_SP_NODE_MISSING, [], b'', None, 0
+    nodes = [blob]
+
+    def end(status, value=b'', at=0):
+        if status == PV_SP_OK and max_nodes is not None and len(nodes) > max_nodes:
+            status = PV_SP_PATH_TOO_LONG
+        if status != PV_SP_OK:
+            return status, nodes, b'', None, 0
+        proof = serialize_nodes(nodes)
+        head = len(proof) - sum(len(n) for n in nodes)
+        return status, nodes, value, proof, (head + at if value else 0)
+
+    cb, ce = 0, len(blob)
+    total, nib = 2 * len(key), 0
+    for _ in range(total + 1):
+        head = _rlp_item(blob, cb, ce)
+        if head is None or not head[0] or head[2] != ce:
+            return end(PV_SP_MALFORMED)
+        items, pos = [], head[1]
+        while pos < ce:
+            if len(items) == 17:
+                return end(PV_SP_MALFORMED)
+            it = _rlp_item(blob, pos, ce)
+            if it is None:
+                return end(PV_SP_MALFORMED)
+            items.append((pos,) + it)      # (start, is_list, payload begin, payload end)
+            pos = it[2]
+        done = False
+        if len(items) == 17:
+            if nib == total:
+                ref, done = items[16], True
+            else:
+                ref = items[_nibble(key, 0, nib)]
+                nib += 1
+        elif len(items) == 2:
+            _, i0l, i0b, i0e = items[0]
+            if i0l or i0e == i0b:
+                return end(PV_SP_MALFORMED)
+            flags = blob[i0b] >> 4
+            odd = flags & 1
+            pn = 2 * (i0e - i0b - 1) + odd
+            skip = 2 - odd
+            left = total - nib
+            leaf = bool(flags & 2)
+            if not leaf and pn == 0:
+                return end(PV_SP_MALFORMED)
+            match = (pn == left) if leaf else (pn <= left)
+            if match:
+                match = all(_nibble(blob, i0b, skip + i) == _nibble(key, 0, nib + i) for i in range(pn))
+            if not match:
+                return end(PV_SP_OK)       # blank: proven absent
+            ref = items[1]
+            if leaf:
+                done = True
+            else:
+                nib += pn
+        else:
+            return end(PV_SP_MALFORMED)
+        rs, rl, rb, re = ref
+        if done:
+            if rl:
+                return end(PV_SP_MALFORMED)
+            return end(PV_SP_OK, bytes(blob[rb:re]), rb)
+        if rl:                              # an inline node: its RLP is the item itself
+            cb, ce = rs, re
+            continue
+        if re == rb:
+            return end(PV_SP_OK)           # blank: proven absent
+        if re - rb != 32:
+            return end(PV_SP_NODE_MISSING)
+        nxt = db.get(bytes(blob[rb:re]))
+        if nxt is None:
+            return end(PV_SP_NODE_MISSING)
+        blob = nxt
+        nodes.append(blob)
+        cb, ce = 0, len(blob)
+    return end(PV_SP_MALFORMED)
+
+
+def root_hash_of(root):
+    """a 32-byte root hash as it is; a decoded root node (what get_head_by_hash returns)
+    RLP-encoded and hashed; the blank node -> BLANK_ROOT"""
+    if isinstance(root, (bytes, bytearray, memoryview)):
+        root = bytes(root)
+        if root == BLANK_NODE:
+            return BLANK_ROOT
+        if len(root) != 32:
+            raise ValueError('a root hash has 32 bytes')
+        return root
+    if isinstance(root, (list, tuple)):
+        return hashlib.sha3_256(rlp_encode(root)).digest()
+    raise TypeError('root is a 32-byte hash or a decoded root node')
+
+
+class Proved:
+    """The arrays of one pv_state_store_prove call."""
+    __slots__ = ('status', 'node_count', 'proof_off', 'val_rel', 'val_len', 'blob')
+
+    def proof(self, q):
+        return self.blob[self.proof_off[q]:self.proof_off[q + 1]].tobytes()
+
+    def value(self, q):
+        o = int(self.proof_off[q] + self.val_rel[q])
+        return self.blob[o:o + int(self.val_len[q])].tobytes()
+
+
+class GpuStateStore:
+    """A device-resident, append-only store of trie nodes keyed by their SHA3-256."""
+
+    def __init__(self, device=0, node_hint=1 << 16, byte_hint=0):
+        nat.ensure_init()
+        self._lib = nat.load()
+        self.device = device
+        h = ctypes.c_int32(0)
+        nat._check('pv_state_store_create', self._lib.pv_state_store_create(node_hint, byte_hint, device,
+                                                                            ctypes.byref(h)))
+        self._id = h.value
+
+    def close(self):
+        if self._id:
+            sid, self._id = self._id, 0
+            nat._check('pv_state_store_free', self._lib.pv_state_store_free(sid))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """{'n_nodes': added, 'n_unique': with a table slot, 'n_bytes', 'n_slots'}"""
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        nat._check('pv_state_store_info', self._lib.pv_state_store_info(self._id, *[ctypes.byref(x) for x in v]))
+        return dict(zip(('n_nodes', 'n_unique', 'n_bytes', 'n_slots'), (x.value for x in v)))
+
+    def add_nodes(self, nodes, want_digests=False):
+        """Add node RLPs (what the host trie stores under their hash on commit) -> the
+        number new to the store; with want_digests -> (that, [32-byte digests])."""
+        nodes = [bytes(n) for n in nodes]
+        if not nodes:
+            return (0, []) if want_digests else 0
+        blob, off = nat.pack_messages(nodes)
+        dig = np.empty((len(nodes), 32), np.uint8) if want_digests else None
+        added = ctypes.c_uint64(0)
+        nat._check('pv_state_store_add', self._lib.pv_state_store_add(self._id, _p(blob), _p(off), len(nodes), _p(dig),
+                                                                      ctypes.byref(added)))
+        if want_digests:
+            return added.value, [dig[i].tobytes() for i in range(len(nodes))]
+        return added.value
+
+    def add_serialized_proof(self, data):
+        """Add the nodes of a serialized proof (rlp(list of nodes)) -> the number new to the store"""
+        data = bytes(data)
+        ranges = rlp_split_list(data)
+        if ranges is None:
+            raise ValueError('not a serialized proof: not one RLP list')
+        return self.add_nodes([data[b:e] for b, e in ranges if e - b > 1])   # 0x80, the blank node, is no node
+
+    def prove(self, roots, root_idx, keys, max_nodes=None, proof_cap=None):
+        """pv_state_store_prove: `roots` 32-byte hashes, root_idx per key (None: root q for
+        key q) -> Proved.  max_nodes defaults to 2 * max key length + 1, the bound of any
+        walk, so PV_SP_PATH_TOO_LONG cannot occur."""
+        keys = [bytes(k) for k in keys]
+        n = len(keys)
+        out = Proved()
+        out.status, out.node_count = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        out.proof_off = np.zeros(n + 1, np.uint64)
+        out.val_rel, out.val_len = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        out.blob = np.zeros(0, np.uint8)
+        if n == 0:
+            return out
+        if max_nodes is None:
+            max_nodes = 2 * max(len(k) for k in keys) + 1
+        rts = np.frombuffer(b''.join(bytes(r) for r in roots), np.uint8)
+        ridx = None if root_idx is None else np.ascontiguousarray(root_idx, np.uint32)
+        kblob, koff = nat.pack_messages(keys)
+        cap = max(1 << 16, 1024 * n) if proof_cap is None else proof_cap
+        for _ in range(2):
+            blob = np.empty(max(cap, 1), np.uint8)
+            rc = self._lib.pv_state_store_prove(self._id, _p(rts), _p(ridx), len(roots), _p(kblob), _p(koff), n,
+                                                max_nodes, _p(out.status), _p(out.node_count), _p(out.proof_off),
+                                                _p(out.val_rel), _p(out.val_len), _p(blob), cap)
+            total = int(out.proof_off[n])
+            # a capacity guessed too small: the offsets are written, the bytes are not
+            if rc == 0 or proof_cap is not None or total <= cap or \
+                    not self._lib.pv_last_error().startswith(b'proof_cap '):
+                break
+            cap = total
+        nat._check('pv_state_store_prove', rc)
+        out.blob = blob[:total]
+        return out
+
+    def generate_state_proofs_batch(self, items):
+        """[(root, key), ...] -> per item (serialized proof, value or None), or None for an
+        item whose root or a node on its path is not in the store (the read handler's
+        (None, None)); one GPU call.  The value is decoded as PruningState.get_decoded does
+        (state/pruning_state.py:162-163)."""
+        items = list(items)
+        index, roots, ridx, keys = {}, [], [], []
+        for root, key in items:
+            rh = root_hash_of(root)
+            ridx.append(index.setdefault(rh, len(index)))
+            if ridx[-1] == len(roots):
+                roots.append(rh)
+            keys.append(key.encode() if isinstance(key, str) else bytes(key))
+        pr = self.prove(roots, ridx, keys)
+        out = []
+        for q in range(len(items)):
+            st = int(pr.status[q])
+            if st == PV_SP_NODE_MISSING:
+                out.append(None)
+            elif st != PV_SP_OK:
+                raise ValueError('item {}: a node on the path is not a well-formed trie node'.format(q))
+            else:
+                out.append((pr.proof(q), rlp_decode(pr.value(q))[0] if pr.val_len[q] else None))
+        return out
+
+    def get_for_root_hash_batch(self, items):
+        """PruningState.get_for_root_hash (state/pruning_state.py:72-77) for [(root, key), ...]:
+        the decoded values, None for an absent key; KeyError for a missing root or node"""
+        out = []
+        for q, r in enumerate(self.generate_state_proofs_batch(items)):
+            if r is None:
+                raise KeyError('item {}: the root or a node on the path is not in the store'.format(q))
+            out.append(r[1])
+        return out
+
+    def generate_state_proof(self, key, root, serialize=False, get_value=False):
+        """PruningState.generate_state_proof for one key.  `root` is a 32-byte root hash or a
+        decoded root node.  -> the proof (serialized bytes, or the list of decoded nodes,
+        root last), with get_value (proof, value as the trie stores it or None).  KeyError
+        where the reference raises it: the root or a node on the path is not in the store."""
+        key = key.encode() if isinstance(key, str) else bytes(key)
+        pr = self.prove([root_hash_of(root)], None, [key])
+        st = int(pr.status[0])
+        if st == PV_SP_NODE_MISSING:
+            raise KeyError('the root or a node on the path is not in the store')
+        if st != PV_SP_OK:
+            raise ValueError('a node on the path is not a well-formed trie node')
+        proof = pr.proof(0)
+        if not serialize:
+            proof = rlp_decode(proof)
+        if not get_value:
+            return proof
+        return proof, (pr.value(0) if pr.val_len[0] else None)
