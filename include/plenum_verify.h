@@ -439,7 +439,7 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
  * order is Python set order.  Blank root: the proof is the empty list, the one byte 0xc0, which
  * is what verify accepts; the reference would serialize [b''].
  * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal), deletion and
- * pruning of nodes, building or updating tries on the device. */
+ * pruning of nodes, updating a trie on the device (building one from a batch: pv_state_build). */
 #define PV_SP_PATH_TOO_LONG 4
 int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t *store_out);
 int pv_state_store_add(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
@@ -459,6 +459,54 @@ int pv_state_store_walk_device(int32_t store, const uint8_t *roots, const uint32
 int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const uint32_t *node_count,
                                uint32_t max_nodes, const uint64_t *proof_off, uint64_t n_queries,
                                uint8_t *proof_blob, void *stream);
+
+/* Batch construction of a state trie (csrc/pv_trie_build.h): the write side of the store above.
+ * The reference computes a state root with one PruningState.set per key and reads headHash
+ * (state/pruning_state.py:60-61, 136; Trie.update, state/trie/pruning_trie.py:1006-1027).  A
+ * Merkle-Patricia root depends on the final key/value set alone, so any sequence of sets is one
+ * batch computation over the sorted distinct keys.
+ *   Input    n keys (key_blob / key_off) and n values (val_blob / val_off); a value is the bytes
+ *            the trie stores, rlp([v]) from PruningState.set, and is not empty.
+ *   Output   root (32 bytes, HOST memory in both forms); *n_nodes and *n_bytes (HOST, may be
+ *            NULL): the nodes the reference stores under their hash -- RLP of >= 32 bytes, and the
+ *            root node whatever its length (_encode_node(..., is_root=True), :334-344) -- and
+ *            their bytes.  Optional, all or some: node_blob (n_bytes), node_off (n_nodes + 1,
+ *            node_off[0] = 0), digests (n_nodes x 32).  Node order is fixed by the keys alone
+ *            (position i of the sorted keys owns, in this order, the extension above the branch
+ *            whose leftmost split is before key i, that branch, and the leaf of key i); two
+ *            byte-identical nodes are both emitted.  n == 0, the empty state: PV_OK, root
+ *            receives SHA3-256(0x80), *n_nodes and *n_bytes 0, node_off[0] = 0 -- each if it is
+ *            given (all may be NULL); no kernel of the build runs, nothing is inserted and the
+ *            store and the input buffers are not looked at.
+ *   Capacities   blob_cap bytes for node_blob; node_cap nodes for node_off (node_cap + 1 entries)
+ *            and digests (node_cap x 32).  A capacity counts only for the outputs it sizes that
+ *            are given (the digests alone need no blob_cap).  If one is too small: PV_EINVAL,
+ *            the text starts with
+ *            "node capacity too small", *n_nodes / *n_bytes hold what is needed, no node is
+ *            written and none is inserted, so the caller can retry.
+ *   store    -1, or a store on the same device: the nodes are appended and inserted with the
+ *            digests the build computed (no second hash).
+ *   pv_state_build (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
+ *            HOST buffers, keys in any order; of equal keys the last occurrence wins, as a
+ *            sequence of sets gives.  PV_EINVAL before any launch: null pointers with n > 0,
+ *            offsets not monotone, an empty value, an unknown store.
+ *   pv_state_build_device (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
+ *            DEVICE buffers (node outputs too).  The keys must be strictly increasing bytewise,
+ *            a proper prefix first; a pair out of order or equal is refused with a text naming
+ *            the first offending index (so are an empty value and decreasing offsets), nothing
+ *            is written and nothing is inserted.  key_blob and val_blob are 4-byte aligned with
+ *            16 readable bytes after the last item; digests 16-byte aligned.
+ * At most 2^28 keys per call, keys of at most 2^20 bytes, values of at most 2^30 bytes.
+ * The empty key is a key like any other (the reference accepts it).  Differences from the
+ * reference: it also keeps the intermediate nodes of every update, here only the nodes reachable
+ * from the final root exist.  Out of scope: applying sets to an existing root, deletion. */
+int pv_state_build(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob, const uint64_t *val_off,
+                   uint64_t n, int32_t store, uint8_t *root, uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob,
+                   uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap, uint8_t *digests);
+int pv_state_build_device(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob,
+                          const uint64_t *val_off, uint64_t n, int32_t store, uint8_t *root, uint64_t *n_nodes,
+                          uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
+                          uint64_t node_cap, uint8_t *digests, int device, void *stream);
 
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of

@@ -27,6 +27,7 @@
 #include "pv_kernels.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
+#include "pv_trie_build.h"
 
 static_assert(pv::SP_OK == PV_SP_OK && pv::SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
                   pv::SP_NODE_MISSING == PV_SP_NODE_MISSING && pv::SP_MALFORMED == PV_SP_MALFORMED,
@@ -3157,6 +3158,267 @@ int pv_state_store_prove(int32_t store, const uint8_t* roots, const uint32_t* ro
                                     dpoff.p, n_queries, dproof.p, merkle_blocks(d), s));
   HIP_OK(hipMemcpyAsync(proof_blob, dproof.p, total, hipMemcpyDeviceToHost, s));
   return tail.finish();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- batch trie build
+namespace {
+
+// The tail of an add for nodes whose digests are known (pv_state_build with a
+// store): copy, k_trie_store_layout, the digests copied instead of a second
+// k_sha3_256, then k_trie_store_insert / k_trie_store_rehash as store_add.
+// blob / off (off[0] = 0, off[n_new] = total) / dig are device memory.
+int store_add_hashed(StateStore& st, Device& d, hipStream_t s, const uint8_t* blob, const uint64_t* off,
+                     const uint32_t* dig, uint64_t n_new, uint64_t total) {
+  if (n_new == 0) return PV_OK;
+  const uint64_t nodes = st.n_nodes + n_new;
+  if (const int rc = store_reserve(st, nodes, st.n_bytes + total, s)) return rc;
+  if (total) HIP_OK(hipMemcpyAsync(st.blob + st.n_bytes, blob, total, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(st.blob + st.n_bytes + total, 0, 16, s));
+  HIP_OK(hipMemsetAsync(st.dup + st.n_nodes, 0, n_new, s));
+  HIP_OK(pv::launch_trie_store_layout(off, n_new, st.n_bytes, total, st.beg, st.end, st.n_nodes, merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(st.dig + 8 * st.n_nodes, dig, n_new * 32, hipMemcpyDeviceToDevice, s));
+  if (nodes > st.slots / 2) {
+    uint64_t ns = st.slots;
+    while (nodes > ns / 2) ns *= 2;
+    if (ns > (1ull << 31)) return fail(PV_ENOMEM, "state store table above 2^31 slots");
+    if (const int rc = store_rehash(st, (uint32_t)ns, d, s)) return rc;
+  }
+  HIP_OK(pv::launch_trie_store_insert(st.table, st.slots, st.dig, st.dup, (uint32_t)st.n_nodes, (uint32_t)n_new,
+                                      st.unique, merkle_blocks(d), s));
+  unsigned int uniq = 0;
+  HIP_OK(hipMemcpyAsync(&uniq, st.unique, 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  st.n_unique = uniq;
+  st.n_nodes = nodes;
+  st.n_bytes += total;
+  return PV_OK;
+}
+
+// The build over device keys and values (sorted, distinct).  root, n_nodes and
+// n_bytes are host memory; node_blob / node_off / digests are host memory with
+// host_out, else device memory; st: the store that takes the nodes, or null.
+int build_core(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, const uint8_t* vb, const uint64_t* vo,
+               uint64_t n, StateStore* st, uint8_t* root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
+               uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, bool host_out) {
+  const hipMemcpyKind out_kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (n_nodes) *n_nodes = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (n == 0) return PV_OK;   // the entry points return before this
+  uint64_t lvoff[pv::TB_MAX_LEVELS + 1];
+  pv::TbCtx c{};
+  c.key_blob = kb;
+  c.key_off = ko;
+  c.val_blob = vb;
+  c.val_off = vo;
+  c.n = n;
+  c.nlv = pv::tb_tree_layout(n, lvoff);
+  const uint64_t ents = 3 * n;
+  TmpBuf<uint32_t> tree, child, lvl, aux, elen, stats, odig;
+  TmpBuf<uint64_t> dlvoff, off, idx, ooff;
+  TmpBuf<uint8_t> inl, oblob;
+  StreamDrain tail{s};
+  HIP_OK(tree.alloc(lvoff[c.nlv]));
+  HIP_OK(dlvoff.put(lvoff, pv::TB_MAX_LEVELS + 1, s));
+  HIP_OK(child.alloc(16 * n));
+  HIP_OK(lvl.alloc(ents));
+  HIP_OK(aux.alloc(ents));
+  HIP_OK(elen.alloc(ents));
+  HIP_OK(off.alloc(ents + 1));
+  HIP_OK(idx.alloc(ents + 1));
+  HIP_OK(inl.alloc(32 * ents));
+  uint32_t hs[5] = {0, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0};   // max h, three first-bad indices, the root's entity
+  HIP_OK(stats.put(hs, 5, s));
+  HIP_OK(hipMemsetAsync(child.p, 0, 16 * n * 4, s));
+  HIP_OK(hipMemsetAsync(off.p, 0, (ents + 1) * 8, s));
+  HIP_OK(hipMemsetAsync(idx.p, 0, (ents + 1) * 8, s));
+  c.tree = tree.p;
+  c.lvoff = dlvoff.p;
+  c.child = child.p;
+  c.lvl = lvl.p;
+  c.aux = aux.p;
+  c.elen = elen.p;
+  c.off = off.p;
+  c.idx = idx.p;
+  c.inl = inl.p;
+  c.root_e = stats.p + 4;
+  const int mb = merkle_blocks(d);
+  HIP_OK(pv::launch_trie_build_lcp(c, stats.p, mb, s));
+  HIP_OK(hipMemcpyAsync(hs, stats.p, 16, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (hs[3] != 0xffffffffu)
+    return fail(PV_EINVAL, "key_off or val_off decreases, or a key is above 2^20 bytes, at index %u", hs[3]);
+  if (hs[2] != 0xffffffffu) return fail(PV_EINVAL, "value %u is empty or above 2^30 bytes", hs[2]);
+  if (hs[1] != 0xffffffffu)
+    return fail(PV_EINVAL, "keys not strictly increasing at index %u (key %u is not above key %u)", hs[1], hs[1],
+                hs[1] - 1);
+  const uint32_t maxh = hs[0];
+  for (uint32_t lv = 1; lv < c.nlv; ++lv) HIP_OK(pv::launch_trie_build_min(c, lv, lvoff[lv + 1] - lvoff[lv], mb, s));
+  HIP_OK(pv::launch_trie_build_struct(c, stats.p + 4, mb, s));
+  for (uint32_t lv = maxh + 1; lv-- > 0;) HIP_OK(pv::launch_trie_build_size(c, lv, mb, s));
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(ents + 1)));
+  HIP_OK(pv::launch_exclusive_scan(off.p, ents + 1, d.scan.p, s));
+  HIP_OK(pv::launch_exclusive_scan(idx.p, ents + 1, d.scan.p, s));
+  uint64_t total = 0, nodes = 0, root_id = 0;
+  uint32_t root_e = 0;
+  HIP_OK(hipMemcpyAsync(&total, off.p + ents, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&nodes, idx.p + ents, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&root_e, stats.p + 4, 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (root_e >= ents || nodes == 0 || nodes > ents) return fail(PV_EIO, "trie build: inconsistent structure pass");
+  HIP_OK(hipMemcpyAsync(&root_id, idx.p + root_e, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (n_nodes) *n_nodes = nodes;
+  if (n_bytes) *n_bytes = total;
+  if ((node_blob && blob_cap < total) || ((node_off || digests) && node_cap < nodes))
+    return fail(PV_EINVAL, "node capacity too small: the build has %llu nodes of %llu bytes", (unsigned long long)nodes,
+                (unsigned long long)total);
+  if (st && (nodes > pv::TS_MAX_NODES || st->n_nodes + nodes > pv::TS_MAX_NODES))
+    return fail(PV_EINVAL, "state store limited to 2^32 - 2 nodes");
+  HIP_OK(oblob.alloc(total + 16));
+  HIP_OK(ooff.alloc(nodes + 1));
+  HIP_OK(odig.alloc(8 * nodes));
+  HIP_OK(hipMemsetAsync(oblob.p + total, 0, 16, s));
+  c.out_blob = oblob.p;
+  c.node_off = ooff.p;
+  c.dig = odig.p;
+  for (uint32_t lv = maxh + 1; lv-- > 0;) HIP_OK(pv::launch_trie_build_emit(c, lv, mb, s));
+  HIP_OK(hipMemcpyAsync(ooff.p + nodes, off.p + ents, 8, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(root, odig.p + 8 * root_id, 32, hipMemcpyDeviceToHost, s));
+  if (node_blob && total) HIP_OK(hipMemcpyAsync(node_blob, oblob.p, total, out_kind, s));
+  if (node_off) HIP_OK(hipMemcpyAsync(node_off, ooff.p, (nodes + 1) * 8, out_kind, s));
+  if (digests) HIP_OK(hipMemcpyAsync(digests, odig.p, nodes * 32, out_kind, s));
+  if (st)
+    if (const int rc = store_add_hashed(*st, d, s, oblob.p, ooff.p, odig.p, nodes, total)) return rc;
+  return tail.finish();
+}
+
+const uint8_t kBlankRoot[32] = {0xbc, 0x20, 0x71, 0xa4, 0xde, 0x84, 0x6f, 0x28, 0x57, 0x02, 0x44,
+                                0x7f, 0x25, 0x89, 0xdd, 0x16, 0x36, 0x78, 0xe0, 0x97, 0x2a, 0x8a,
+                                0x1b, 0x0d, 0x28, 0xb0, 0x4e, 0xd5, 0xc0, 0x94, 0x54, 0x7f};   // SHA3-256(0x80)
+
+// The empty batch: the blank root, no nodes.  Every output that is given is
+// written; nothing is launched for the build and nothing is inserted, so the
+// store is not looked at.
+int build_empty(Entry& en, void* stream, uint8_t* root, uint64_t* n_nodes, uint64_t* n_bytes, uint64_t* node_off,
+                bool host_out) {
+  if (root) memcpy(root, kBlankRoot, 32);
+  if (n_nodes) *n_nodes = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (!node_off) return PV_OK;
+  if (host_out) {
+    node_off[0] = 0;
+    return PV_OK;
+  }
+  if (const int rc = en.begin(stream)) return rc;
+  HIP_OK(hipMemsetAsync(node_off, 0, 8, en.s));
+  return en.finish();
+}
+
+// key a before key b: bytewise, a proper prefix first
+bool key_less(const uint8_t* blob, const uint64_t* off, uint64_t a, uint64_t b, bool* equal) {
+  const uint64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
+  const uint64_t m = la < lb ? la : lb;
+  const int c = m ? memcmp(blob + off[a], blob + off[b], m) : 0;
+  *equal = c == 0 && la == lb;
+  return c < 0 || (c == 0 && la < lb);
+}
+
+}  // namespace
+
+extern "C" {
+
+// PruningState.set per pair and headHash (state/pruning_state.py:60-61, 136; Trie.update,
+// state/trie/pruning_trie.py:1006-1027) as one batch; see include/plenum_verify.h.
+int pv_state_build_device(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
+                          const uint64_t* val_off, uint64_t n, int32_t store, uint8_t* root, uint64_t* n_nodes,
+                          uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                          uint64_t node_cap, uint8_t* digests, int device, void* stream) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (n == 0) return build_empty(en, stream, root, n_nodes, n_bytes, node_off, false);
+  if (!root) return fail(PV_EINVAL, "null pointer");
+  if (!key_blob || !key_off || !val_blob || !val_off) return fail(PV_EINVAL, "null device buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  if ((reinterpret_cast<uintptr_t>(key_blob) & 3u) || (reinterpret_cast<uintptr_t>(val_blob) & 3u))
+    return fail(PV_EINVAL, "key_blob and val_blob must be 4-byte aligned");
+  if (digests && misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  StateStore* st = nullptr;
+  if (store != -1) {
+    st = find_store(store);
+    if (!st) return fail(PV_EINVAL, "no state store with id %d", (int)store);
+    if (st->dev != en.d->id)
+      return fail(PV_EINVAL, "state store %d lives on device %d, not on device %d", (int)store, st->dev, device);
+  }
+  if (const int rc = en.begin(stream)) return rc;
+  return build_core(*en.d, en.s, key_blob, key_off, val_blob, val_off, n, st, root, n_nodes, n_bytes, node_blob,
+                    blob_cap, node_off, node_cap, digests, false);
+}
+
+// The host form of the same (state/pruning_state.py:60-61; state/trie/pruning_trie.py:1006-1027):
+// keys in any order, the last of equal keys wins, as a sequence of sets gives.
+int pv_state_build(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
+                   uint64_t n, int32_t store, uint8_t* root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
+                   uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests) {
+  if (n == 0) {
+    Entry en;
+    if (const int rc = en.check()) return rc;
+    return build_empty(en, nullptr, root, n_nodes, n_bytes, node_off, true);
+  }
+  // The argument checks and the sorted copy touch no library state: they run
+  // before the library lock is taken, so a large sort blocks no other call.
+  if (!root) return fail(PV_EINVAL, "null pointer");
+  if (!key_off || !val_off || !val_blob) return fail(PV_EINVAL, "null buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  Ragged keys(key_off, n), vals(val_off, n);
+  if (const int rc = keys.check("key_off")) return rc;
+  if (const int rc = vals.check("val_off")) return rc;
+  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
+  for (uint64_t i = 0; i < n; ++i) {
+    if (val_off[i + 1] == val_off[i]) return fail(PV_EINVAL, "value %llu is empty", (unsigned long long)i);
+    if (key_off[i + 1] - key_off[i] > pv::TB_MAX_KEY_BYTES || val_off[i + 1] - val_off[i] > pv::TB_MAX_VAL_BYTES)
+      return fail(PV_EINVAL, "pair %llu: a key above 2^20 or a value above 2^30 bytes", (unsigned long long)i);
+  }
+  // sorted index; of equal keys the last occurrence stays
+  std::vector<uint64_t> order(n), pick;
+  for (uint64_t i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    bool eq;
+    return key_less(key_blob, key_off, a, b, &eq);
+  });
+  for (uint64_t k = 0; k < n; ++k) {
+    bool eq = false;
+    if (k + 1 < n) (void)key_less(key_blob, key_off, order[k], order[k + 1], &eq);
+    if (!eq) pick.push_back(order[k]);
+  }
+  const uint64_t m = pick.size();
+  std::vector<uint64_t> ko(m + 1, 0), vo(m + 1, 0);
+  for (uint64_t k = 0; k < m; ++k) {
+    ko[k + 1] = ko[k] + (key_off[pick[k] + 1] - key_off[pick[k]]);
+    vo[k + 1] = vo[k] + (val_off[pick[k] + 1] - val_off[pick[k]]);
+  }
+  std::vector<uint8_t> kb(ko[m] + 16, 0), vb(vo[m] + 16, 0);
+  for (uint64_t k = 0; k < m; ++k) {
+    if (ko[k + 1] > ko[k]) memcpy(&kb[ko[k]], key_blob + key_off[pick[k]], ko[k + 1] - ko[k]);
+    memcpy(&vb[vo[k]], val_blob + val_off[pick[k]], vo[k + 1] - vo[k]);
+  }
+  Entry en;
+  if (const int rc = en.check()) return rc;
+  StateStore* st = nullptr;
+  if (store != -1)
+    if (const int rc = store_enter(en, store, &st)) return rc;
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> dkb, dvb;
+  TmpBuf<uint64_t> dko, dvo;
+  StreamDrain tail{s};
+  HIP_OK(dkb.put(kb.data(), kb.size(), s));
+  HIP_OK(dvb.put(vb.data(), vb.size(), s));
+  HIP_OK(dko.put(ko.data(), m + 1, s));
+  HIP_OK(dvo.put(vo.data(), m + 1, s));
+  return build_core(*en.d, s, dkb.p, dko.p, dvb.p, dvo.p, m, st, root, n_nodes, n_bytes, node_blob, blob_cap, node_off,
+                    node_cap, digests, true);
 }
 
 }  // extern "C"

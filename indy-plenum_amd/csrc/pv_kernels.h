@@ -230,6 +230,18 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
                                   const uint64_t* proof_off, uint64_t n_queries, uint8_t* proof_blob, int max_blocks,
                                   hipStream_t s);
 
+// Batch trie build (pv_trie_build.h); all device memory.  One item per lane of the routine
+// named: tb_lcp_one over positions 0 .. n (stats[0] <- max h by atomicMax, stats[1 .. 3] <- the
+// first index refused for order / value / offsets by atomicMin), tb_min_one over the `size`
+// entries of tree level lv, tb_struct_one over the keys (*root_e <- the root's entity),
+// tb_size_one / tb_emit_one over the entities of level lv.
+struct TbCtx;
+hipError_t launch_trie_build_lcp(const TbCtx& c, uint32_t* stats, int max_blocks, hipStream_t s);
+hipError_t launch_trie_build_min(const TbCtx& c, uint32_t lv, uint64_t size, int max_blocks, hipStream_t s);
+hipError_t launch_trie_build_struct(const TbCtx& c, uint32_t* root_e, int max_blocks, hipStream_t s);
+hipError_t launch_trie_build_size(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s);
+hipError_t launch_trie_build_emit(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

@@ -19,6 +19,7 @@
 #include "pv_sha3.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
+#include "pv_trie_build.h"
 #include "pv_kernels.h"
 #include "plenum_verify.h"
 
@@ -1928,6 +1929,78 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
   if (n_queries == 0) return hipSuccess;
   hipLaunchKernelGGL(k_trie_proof_pack, dim3(mp_grid(n_queries * 64, max_blocks)), dim3(256), 0, s, blob, beg,
                      end, n_nodes, node_ids, node_count, max_nodes, proof_off, n_queries, proof_blob);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- batch trie build
+// pv_trie_build.h: one routine per kernel, one item per lane; the host twin
+// calls the same routines in index order.  stats[0] = the largest h,
+// stats[1 .. 3] = the first index refused for key order / its value / its
+// offsets (0xffffffff: none).
+__global__ __launch_bounds__(256) void k_trie_build_lcp(TbCtx c, uint32_t* __restrict__ stats) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i <= c.n; i += stride) {
+    uint32_t bad;
+    const uint32_t h = tb_lcp_one(c, i, bad);
+    c.tree[i] = h;
+    atomicMax(stats, h);
+    if (bad & TB_BAD_ORDER) atomicMin(stats + 1, (uint32_t)i);
+    if (bad & TB_BAD_VALUE) atomicMin(stats + 2, (uint32_t)i);
+    if (bad & TB_BAD_OFFSET) atomicMin(stats + 3, (uint32_t)i);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_trie_build_min(TbCtx c, uint32_t lv, uint64_t size) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < size; j += stride) tb_min_one(c, lv, j);
+}
+
+__global__ __launch_bounds__(256) void k_trie_build_struct(TbCtx c, uint32_t* __restrict__ root_e) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < c.n; i += stride) {
+    const uint32_t r = tb_struct_one(c, i);
+    if (r) *root_e = r - 1;   // exactly one position owns the root
+  }
+}
+
+__global__ __launch_bounds__(256) void k_trie_build_size(TbCtx c, uint32_t lv) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256, ents = 3 * c.n;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < ents; e += stride)
+    if (c.lvl[e] == lv) tb_size_one(c, (uint32_t)e);
+}
+
+__global__ __launch_bounds__(256) void k_trie_build_emit(TbCtx c, uint32_t lv) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256, ents = 3 * c.n;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < ents; e += stride)
+    if (c.lvl[e] == lv) tb_emit_one(c, (uint32_t)e);
+}
+
+hipError_t launch_trie_build_lcp(const TbCtx& c, uint32_t* stats, int max_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_trie_build_lcp, dim3(mp_grid(c.n + 1, max_blocks)), dim3(256), 0, s, c, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_build_min(const TbCtx& c, uint32_t lv, uint64_t size, int max_blocks, hipStream_t s) {
+  if (size == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_build_min, dim3(mp_grid(size, max_blocks)), dim3(256), 0, s, c, lv, size);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_build_struct(const TbCtx& c, uint32_t* root_e, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_build_struct, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c, root_e);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_build_size(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_build_size, dim3(mp_grid(3 * c.n, max_blocks)), dim3(256), 0, s, c, lv);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_build_emit(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_build_emit, dim3(mp_grid(3 * c.n, max_blocks)), dim3(256), 0, s, c, lv);
   return hipGetLastError();
 }
 

@@ -20,7 +20,8 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
   state_proofs    GpuStateVerifier (+ verify_state_proofs_batch), sha3_256_batch
                   state/pruning_state.py, state/trie/pruning_trie.py
   state_store     GpuStateStore: a device-resident trie node store,
-                  generate_state_proof (+ generate_state_proofs_batch)
+                  generate_state_proof (+ generate_state_proofs_batch), build_state,
+                  state_root_batch
                   state/pruning_state.py, state/trie/pruning_trie.py
   serialization, base58, exceptions, constants   the data formats either side
 
@@ -32,7 +33,7 @@ __version__ = '0.1.0'
 # exported from merkle_proofs, imported on first use (the package import stays light)
 _MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
 _STATE_PROOFS = ('GpuStateVerifier', 'verify_state_proofs_batch', 'sha3_256_batch')
-_STATE_STORE = ('GpuStateStore',)
+_STATE_STORE = ('GpuStateStore', 'state_root_batch')
 __all__ = list(_MERKLE_PROOFS + _STATE_PROOFS + _STATE_STORE)
 
 

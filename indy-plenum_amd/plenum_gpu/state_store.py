@@ -33,11 +33,17 @@ the rest of the reference's order is Python set order.  Blank root: the proof is
 empty list (serialized: the one byte 0xc0), which is what the verifier accepts; the
 reference would return [b''].
 
+* `GpuStateStore.build_state(items)` / `state_root_batch(items)` -- pv_state_build: a whole
+  trie from a batch of (key, value) pairs (csrc/pv_trie_build.h), the result of one
+  PruningState.set per pair (state/pruning_state.py:60-61, Trie.update,
+  state/trie/pruning_trie.py:1006-1027); `build_host(items)` is its pure-Python mirror.
+
 Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal),
-deletion and pruning of nodes, building or updating tries on the device.
+deletion and pruning of nodes, applying sets to an existing root on the device.
 """
 import ctypes
 import hashlib
+import sys
 
 import numpy as np
 
@@ -46,6 +52,10 @@ from .state_proofs import (BLANK_NODE, BLANK_ROOT, PV_SP_MALFORMED, PV_SP_NODE_M
                            _nibble, _p, _rlp_item, rlp_encode, rlp_split_list)
 
 PV_SP_PATH_TOO_LONG = 4   # include/plenum_verify.h
+
+# Size dispatch of state_root_batch, as state_proofs.GPU_MIN_ITEMS (not a fallback): below this
+# many pairs the Python mirror is quicker than one pv_state_build call.
+BUILD_GPU_MIN_ITEMS = 160
 
 
 def rlp_decode(data):
@@ -170,6 +180,123 @@ def walk_host(db, root, key, max_nodes=None):
     return end(PV_SP_MALFORMED)
 
 
+def _hex_prefix(nibbles, leaf):
+    """pack_nibbles (state/trie/pruning_trie.py): flag nibble 2 = leaf, 1 = odd length"""
+    flags = (2 if leaf else 0) + (len(nibbles) & 1)
+    nib = ([flags] if len(nibbles) & 1 else [flags, 0]) + list(nibbles)
+    return bytes(16 * nib[i] + nib[i + 1] for i in range(0, len(nib), 2))
+
+
+def _pairs(items):
+    """(key, raw value) pairs -> sorted [(key, rlp([value]))], the last of equal keys kept"""
+    last = {}
+    for key, value in items:
+        key = key.encode() if isinstance(key, str) else bytes(key)
+        value = value.encode() if isinstance(value, str) else bytes(value)
+        if not value:
+            raise ValueError('an empty value removes a key; a build takes values only')
+        last[key] = rlp_encode([value])
+    return sorted(last.items())
+
+
+def build_encoded_host(pairs):
+    """The build of csrc/pv_trie_build.h in Python over sorted distinct (key, encoded value)
+    pairs -> (root, {sha3(node RLP): node RLP}): the nodes of >= 32 bytes and the root node.
+    A run of keys that share `depth` nibbles is one node: a leaf for one key, else the branch
+    at the depth where the run splits, under an extension if that is deeper than `depth`."""
+    db = {}
+    keys = [[n for b in k for n in (b >> 4, b & 15)] for k, _ in pairs]
+
+    def ref(node, root=False):
+        enc = rlp_encode(node)
+        if len(enc) < 32 and not root:
+            return node
+        h = hashlib.sha3_256(enc).digest()
+        db[h] = enc
+        return h
+
+    def node_of(lo, hi, depth):
+        if hi - lo == 1:
+            return [_hex_prefix(keys[lo][depth:], True), pairs[lo][1]]
+        first, last = keys[lo], keys[hi - 1]     # sorted: the run's common prefix is theirs
+        d = depth
+        while d < len(first) and d < len(last) and first[d] == last[d]:
+            d += 1
+        if d > depth:
+            return [_hex_prefix(first[depth:d], False), ref(node_of(lo, hi, d))]
+        slots, value = [b''] * 16, b''
+        if len(first) == depth:                  # the key that is the run's prefix: the value slot
+            value = pairs[lo][1]
+            lo += 1
+        while lo < hi:
+            nib, end = keys[lo][depth], lo
+            while end < hi and keys[end][depth] == nib:
+                end += 1
+            slots[nib] = ref(node_of(lo, end, depth + 1))
+            lo = end
+        return slots + [value]
+
+    if not pairs:
+        return BLANK_ROOT, db
+    # node_of recurses once per trie level, at most 2 * key length + 1 deep: raise the
+    # interpreter's limit for this call only when keys of hundreds of bytes need it
+    limit, need = sys.getrecursionlimit(), 2 * max(len(k) for k in keys) + 100
+    if limit < need:
+        sys.setrecursionlimit(need)
+    try:
+        return ref(node_of(0, len(pairs), 0), root=True), db
+    finally:
+        if limit < need:
+            sys.setrecursionlimit(limit)
+
+
+def build_host(items):
+    """(key, raw value) pairs in any order, the last of equal keys wins -> (root, {hash: node
+    RLP}): what PruningState.set of every pair leaves reachable from headHash.  The mirror of
+    pv_state_build, used by the CPU tests and below BUILD_GPU_MIN_ITEMS."""
+    return build_encoded_host(_pairs(items))
+
+
+def _root_ptr(root):
+    return root.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def _build_gpu(pairs, store_id, want_nodes=False):
+    """pv_state_build over (key, encoded value) pairs -> (root, n_nodes, n_bytes[, blob, off, digests])"""
+    nat.ensure_init()
+    lib = nat.load()
+    n = len(pairs)
+    kblob, koff = nat.pack_messages([k for k, _ in pairs])
+    vblob, voff = nat.pack_messages([v for _, v in pairs])
+    root = np.zeros(32, np.uint8)
+    nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(blob, bcap, off, ncap, dig):
+        return lib.pv_state_build(_p(kblob), _p(koff), _p(vblob), _p(voff), n, store_id, _root_ptr(root), ctypes.byref(nn),
+                                  ctypes.byref(nb), _p(blob), bcap, _p(off), ncap, _p(dig))
+    if not want_nodes:
+        nat._check('pv_state_build', call(None, 0, None, 0, None))
+        return root.tobytes(), nn.value, nb.value
+    if store_id != -1:
+        raise ValueError('the sizing call and the retry would insert twice')
+    nat._check('pv_state_build', call(None, 0, None, 0, None))   # sizes
+    blob = np.zeros(max(nb.value, 1), np.uint8)
+    off = np.zeros(nn.value + 1, np.uint64)
+    dig = np.zeros((max(nn.value, 1), 32), np.uint8)
+    nat._check('pv_state_build', call(blob, nb.value, off, nn.value, dig))
+    return root.tobytes(), nn.value, nb.value, blob[:nb.value], off, dig[:nn.value]
+
+
+def state_root_batch(items):
+    """The state root after PruningState.set of every (key, raw value) pair (state/pruning_state.py
+    :60-61), the last of equal keys winning; no node is kept.  One pv_state_build call from
+    BUILD_GPU_MIN_ITEMS pairs on, the mirror below."""
+    pairs = _pairs(items)
+    if len(pairs) < BUILD_GPU_MIN_ITEMS:
+        return build_encoded_host(pairs)[0]
+    return _build_gpu(pairs, -1)[0]
+
+
 def root_hash_of(root):
     """a 32-byte root hash as it is; a decoded root node (what get_head_by_hash returns)
     RLP-encoded and hashed; the blank node -> BLANK_ROOT"""
@@ -240,6 +367,12 @@ class GpuStateStore:
         if want_digests:
             return added.value, [dig[i].tobytes() for i in range(len(nodes))]
         return added.value
+
+    def build_state(self, items):
+        """Build the trie of (key, raw value) pairs on the device (pv_state_build) and insert its
+        nodes -> the root hash.  Afterwards generate_state_proof(key, root, ...) and
+        get_for_root_hash_batch work at that root; no host trie is involved."""
+        return _build_gpu(_pairs(items), self._id)[0]
 
     def add_serialized_proof(self, data):
         """Add the nodes of a serialized proof (rlp(list of nodes)) -> the number new to the store"""
