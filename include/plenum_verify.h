@@ -439,7 +439,8 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
  * order is Python set order.  Blank root: the proof is the empty list, the one byte 0xc0, which
  * is what verify accepts; the reference would serialize [b''].
  * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal), deletion and
- * pruning of nodes, updating a trie on the device (building one from a batch: pv_state_build). */
+ * pruning of nodes (building a trie from a batch: pv_state_build; sets onto a committed root:
+ * pv_state_update). */
 #define PV_SP_PATH_TOO_LONG 4
 int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t *store_out);
 int pv_state_store_add(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
@@ -499,7 +500,8 @@ int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const ui
  * At most 2^28 keys per call, keys of at most 2^20 bytes, values of at most 2^30 bytes.
  * The empty key is a key like any other (the reference accepts it).  Differences from the
  * reference: it also keeps the intermediate nodes of every update, here only the nodes reachable
- * from the final root exist.  Out of scope: applying sets to an existing root, deletion. */
+ * from the final root exist.  Sets onto an existing root: pv_state_update below.  Out of scope:
+ * deletion. */
 int pv_state_build(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob, const uint64_t *val_off,
                    uint64_t n, int32_t store, uint8_t *root, uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob,
                    uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap, uint8_t *digests);
@@ -507,6 +509,53 @@ int pv_state_build_device(const uint8_t *key_blob, const uint64_t *key_off, cons
                           const uint64_t *val_off, uint64_t n, int32_t store, uint8_t *root, uint64_t *n_nodes,
                           uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
                           uint64_t node_cap, uint8_t *digests, int device, void *stream);
+
+/* Sets applied to a committed root (csrc/pv_trie_update.h): the per-3PC-batch update.  The
+ * reference takes the state at a committed root, applies one PruningState.set per request of
+ * the batch and reads the new headHash (state/pruning_state.py:60-61, 136; Trie.update,
+ * state/trie/pruning_trie.py:1006-1027).  Here the batch is one call: one lane per batch key
+ * walks the old trie in `store` from old_root and carries, as it is, the reference of every
+ * child no batch key enters; the carried values and references and the new values make one
+ * sorted list, and the build above runs over it.  No host trie and no other key of the state is
+ * needed, and every earlier root stays provable: the store only grows.
+ *   Input    store: where the old trie is read.  old_root (32 bytes, HOST memory in both forms).
+ *            Keys and values as pv_state_build[_device].
+ *   insert   != 0: the emitted nodes are appended to `store` with the digests the build computed.
+ *            0: compute only, so a sizing call followed by a retry never inserts twice.
+ *   Output   new_root (32 bytes, HOST in both forms), *n_nodes, *n_bytes, node_blob, node_off,
+ *            digests and the two capacities as pv_state_build, the "node capacity too small"
+ *            refusal included.  The nodes are exactly what the build over the merged list emits,
+ *            in its fixed order: every re-encoded node on a touched path, the root last changed
+ *            included; nodes inside untouched subtrees are never emitted.  A re-encoded node the
+ *            store already holds (an overwrite with the same value) is emitted and flagged a
+ *            duplicate by the store.  n == 0: PV_OK, new_root = old_root, sizes 0 and
+ *            node_off[0] = 0 -- each if it is given (all may be NULL); no kernel of the update
+ *            runs and, as with the empty build, the store is not looked at.
+ *            old_root = SHA3-256(0x80), the blank root: the result of pv_state_build, and the
+ *            store is not read.
+ *   Refusals   PV_EINVAL before any launch: an unknown store, null pointers with n > 0, offsets
+ *            not monotone, an empty value, misaligned device blobs; PV_ENOTINIT without pv_init.
+ *            The device form refuses unsorted or equal keys, an empty value and decreasing
+ *            offsets with pv_state_build_device's texts.  If the walk of a batch key meets a node
+ *            that is not in the store (old_root included) or is not a well-formed trie node, the
+ *            whole call is refused: PV_EINVAL, the text names the first such key and its PV_SP_*
+ *            status, nothing is written and nothing is inserted.  More than 2^28 merged items
+ *            (batch keys plus carried values and references, at most 17 per node on a key's
+ *            path) are refused.
+ *   pv_state_update (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
+ *            HOST buffers, keys in any order, the last of equal keys wins.
+ *   pv_state_update_device (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
+ *            DEVICE buffers (node outputs too), keys strictly increasing, on the store's device.
+ * Calls are synchronous and ordered on the store's stream (NULL = the library's).  Sets only.
+ * Out of scope: deletion (a set of the empty value), pruning of nodes no root reaches. */
+int pv_state_update(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
+                    const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
+                    uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
+                    uint64_t node_cap, uint8_t *digests);
+int pv_state_update_device(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
+                           const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert,
+                           uint8_t *new_root, uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob,
+                           uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap, uint8_t *digests, void *stream);
 
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of

@@ -28,6 +28,7 @@
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
 #include "pv_trie_build.h"
+#include "pv_trie_update.h"
 
 static_assert(pv::SP_OK == PV_SP_OK && pv::SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
                   pv::SP_NODE_MISSING == PV_SP_NODE_MISSING && pv::SP_MALFORMED == PV_SP_MALFORMED,
@@ -3196,12 +3197,24 @@ int store_add_hashed(StateStore& st, Device& d, hipStream_t s, const uint8_t* bl
   return PV_OK;
 }
 
+// what k_trie_build_lcp refused: hs[1 .. 3] = the first index for order / value / offsets
+int lcp_refusal(const uint32_t* hs) {
+  if (hs[3] != 0xffffffffu)
+    return fail(PV_EINVAL, "key_off or val_off decreases, or a key is above 2^20 bytes, at index %u", hs[3]);
+  if (hs[2] != 0xffffffffu) return fail(PV_EINVAL, "value %u is empty or above 2^30 bytes", hs[2]);
+  if (hs[1] != 0xffffffffu)
+    return fail(PV_EINVAL, "keys not strictly increasing at index %u (key %u is not above key %u)", hs[1], hs[1],
+                hs[1] - 1);
+  return PV_OK;
+}
+
 // The build over device keys and values (sorted, distinct).  root, n_nodes and
 // n_bytes are host memory; node_blob / node_off / digests are host memory with
 // host_out, else device memory; st: the store that takes the nodes, or null.
 int build_core(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, const uint8_t* vb, const uint64_t* vo,
                uint64_t n, StateStore* st, uint8_t* root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
-               uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, bool host_out) {
+               uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, bool host_out,
+               const uint32_t* knib = nullptr, const uint8_t* kind = nullptr) {
   const hipMemcpyKind out_kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   if (n_nodes) *n_nodes = 0;
   if (n_bytes) *n_bytes = 0;
@@ -3213,6 +3226,8 @@ int build_core(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, 
   c.val_blob = vb;
   c.val_off = vo;
   c.n = n;
+  c.knib = knib;   // a merged item list (update_core), else null
+  c.kind = kind;
   c.nlv = pv::tb_tree_layout(n, lvoff);
   const uint64_t ents = 3 * n;
   TmpBuf<uint32_t> tree, child, lvl, aux, elen, stats, odig;
@@ -3247,12 +3262,10 @@ int build_core(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, 
   HIP_OK(pv::launch_trie_build_lcp(c, stats.p, mb, s));
   HIP_OK(hipMemcpyAsync(hs, stats.p, 16, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
-  if (hs[3] != 0xffffffffu)
-    return fail(PV_EINVAL, "key_off or val_off decreases, or a key is above 2^20 bytes, at index %u", hs[3]);
-  if (hs[2] != 0xffffffffu) return fail(PV_EINVAL, "value %u is empty or above 2^30 bytes", hs[2]);
-  if (hs[1] != 0xffffffffu)
-    return fail(PV_EINVAL, "keys not strictly increasing at index %u (key %u is not above key %u)", hs[1], hs[1],
-                hs[1] - 1);
+  if (knib && (hs[1] & hs[2] & hs[3]) != 0xffffffffu)
+    return fail(PV_EIO, "trie update: the merged list is not one a build takes (item %u)",
+                hs[3] < hs[2] ? (hs[3] < hs[1] ? hs[3] : hs[1]) : (hs[2] < hs[1] ? hs[2] : hs[1]));
+  if (const int rc = lcp_refusal(hs)) return rc;
   const uint32_t maxh = hs[0];
   for (uint32_t lv = 1; lv < c.nlv; ++lv) HIP_OK(pv::launch_trie_build_min(c, lv, lvoff[lv + 1] - lvoff[lv], mb, s));
   HIP_OK(pv::launch_trie_build_struct(c, stats.p + 4, mb, s));
@@ -3325,6 +3338,50 @@ bool key_less(const uint8_t* blob, const uint64_t* off, uint64_t a, uint64_t b, 
   return c < 0 || (c == 0 && la < lb);
 }
 
+// The host forms' input: the checks of the arrays, then the pairs sorted with
+// the last of equal keys kept, as blobs with 16 spare bytes and offsets from 0.
+int sorted_pairs(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
+                 uint64_t n, std::vector<uint64_t>& ko, std::vector<uint64_t>& vo, std::vector<uint8_t>& kb,
+                 std::vector<uint8_t>& vb) {
+  if (!key_off || !val_off || !val_blob) return fail(PV_EINVAL, "null buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  Ragged keys(key_off, n), vals(val_off, n);
+  if (const int rc = keys.check("key_off")) return rc;
+  if (const int rc = vals.check("val_off")) return rc;
+  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
+  for (uint64_t i = 0; i < n; ++i) {
+    if (val_off[i + 1] == val_off[i]) return fail(PV_EINVAL, "value %llu is empty", (unsigned long long)i);
+    if (key_off[i + 1] - key_off[i] > pv::TB_MAX_KEY_BYTES || val_off[i + 1] - val_off[i] > pv::TB_MAX_VAL_BYTES)
+      return fail(PV_EINVAL, "pair %llu: a key above 2^20 or a value above 2^30 bytes", (unsigned long long)i);
+  }
+  // sorted index; of equal keys the last occurrence stays
+  std::vector<uint64_t> order(n), pick;
+  for (uint64_t i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    bool eq;
+    return key_less(key_blob, key_off, a, b, &eq);
+  });
+  for (uint64_t k = 0; k < n; ++k) {
+    bool eq = false;
+    if (k + 1 < n) (void)key_less(key_blob, key_off, order[k], order[k + 1], &eq);
+    if (!eq) pick.push_back(order[k]);
+  }
+  const uint64_t m = pick.size();
+  ko.assign(m + 1, 0);
+  vo.assign(m + 1, 0);
+  for (uint64_t k = 0; k < m; ++k) {
+    ko[k + 1] = ko[k] + (key_off[pick[k] + 1] - key_off[pick[k]]);
+    vo[k + 1] = vo[k] + (val_off[pick[k] + 1] - val_off[pick[k]]);
+  }
+  kb.assign(ko[m] + 16, 0);
+  vb.assign(vo[m] + 16, 0);
+  for (uint64_t k = 0; k < m; ++k) {
+    if (ko[k + 1] > ko[k]) memcpy(&kb[ko[k]], key_blob + key_off[pick[k]], ko[k + 1] - ko[k]);
+    memcpy(&vb[vo[k]], val_blob + val_off[pick[k]], vo[k + 1] - vo[k]);
+  }
+  return PV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3369,40 +3426,10 @@ int pv_state_build(const uint8_t* key_blob, const uint64_t* key_off, const uint8
   // The argument checks and the sorted copy touch no library state: they run
   // before the library lock is taken, so a large sort blocks no other call.
   if (!root) return fail(PV_EINVAL, "null pointer");
-  if (!key_off || !val_off || !val_blob) return fail(PV_EINVAL, "null buffer");
-  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
-  Ragged keys(key_off, n), vals(val_off, n);
-  if (const int rc = keys.check("key_off")) return rc;
-  if (const int rc = vals.check("val_off")) return rc;
-  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
-  for (uint64_t i = 0; i < n; ++i) {
-    if (val_off[i + 1] == val_off[i]) return fail(PV_EINVAL, "value %llu is empty", (unsigned long long)i);
-    if (key_off[i + 1] - key_off[i] > pv::TB_MAX_KEY_BYTES || val_off[i + 1] - val_off[i] > pv::TB_MAX_VAL_BYTES)
-      return fail(PV_EINVAL, "pair %llu: a key above 2^20 or a value above 2^30 bytes", (unsigned long long)i);
-  }
-  // sorted index; of equal keys the last occurrence stays
-  std::vector<uint64_t> order(n), pick;
-  for (uint64_t i = 0; i < n; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
-    bool eq;
-    return key_less(key_blob, key_off, a, b, &eq);
-  });
-  for (uint64_t k = 0; k < n; ++k) {
-    bool eq = false;
-    if (k + 1 < n) (void)key_less(key_blob, key_off, order[k], order[k + 1], &eq);
-    if (!eq) pick.push_back(order[k]);
-  }
-  const uint64_t m = pick.size();
-  std::vector<uint64_t> ko(m + 1, 0), vo(m + 1, 0);
-  for (uint64_t k = 0; k < m; ++k) {
-    ko[k + 1] = ko[k] + (key_off[pick[k] + 1] - key_off[pick[k]]);
-    vo[k + 1] = vo[k] + (val_off[pick[k] + 1] - val_off[pick[k]]);
-  }
-  std::vector<uint8_t> kb(ko[m] + 16, 0), vb(vo[m] + 16, 0);
-  for (uint64_t k = 0; k < m; ++k) {
-    if (ko[k + 1] > ko[k]) memcpy(&kb[ko[k]], key_blob + key_off[pick[k]], ko[k + 1] - ko[k]);
-    memcpy(&vb[vo[k]], val_blob + val_off[pick[k]], vo[k + 1] - vo[k]);
-  }
+  std::vector<uint64_t> ko, vo;
+  std::vector<uint8_t> kb, vb;
+  if (const int rc = sorted_pairs(key_blob, key_off, val_blob, val_off, n, ko, vo, kb, vb)) return rc;
+  const uint64_t m = ko.size() - 1;
   Entry en;
   if (const int rc = en.check()) return rc;
   StateStore* st = nullptr;
@@ -3419,6 +3446,181 @@ int pv_state_build(const uint8_t* key_blob, const uint64_t* key_off, const uint8
   HIP_OK(dvo.put(vo.data(), m + 1, s));
   return build_core(*en.d, s, dkb.p, dko.p, dvb.p, dvo.p, m, st, root, n_nodes, n_bytes, node_blob, blob_cap, node_off,
                     node_cap, digests, true);
+}
+
+}  // extern "C"
+
+// ------------------------------------------- sets onto a committed root
+namespace {
+
+// The update over device keys and values (sorted, distinct): the merge of
+// pv_trie_update.h, then build_core over the merged items.  old_root, root,
+// n_nodes and n_bytes are host memory; the node outputs as build_core's.
+int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_root, const uint8_t* kb,
+                const uint64_t* ko, const uint8_t* vb, const uint64_t* vo, uint64_t n, bool insert, uint8_t* root,
+                uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                uint64_t node_cap, uint8_t* digests, bool host_out) {
+  if (memcmp(old_root, kBlankRoot, 32) == 0)   // nothing to merge with: the store is not read
+    return build_core(d, s, kb, ko, vb, vo, n, insert ? &st : nullptr, root, n_nodes, n_bytes, node_blob, blob_cap,
+                      node_off, node_cap, digests, host_out);
+  if (n_nodes) *n_nodes = 0;
+  if (n_bytes) *n_bytes = 0;
+  const int mb = merkle_blocks(d);
+  TmpBuf<uint32_t> h, stats, droot, inib;
+  TmpBuf<uint64_t> sizes, ikoff, ivoff;
+  TmpBuf<uint8_t> status, ikey, ival, ikind;
+  StreamDrain tail{s};
+  // the batch's own checks and h[], by the build's first kernel: the same refusals
+  pv::TbCtx b{};
+  b.key_blob = kb;
+  b.key_off = ko;
+  b.val_blob = vb;
+  b.val_off = vo;
+  b.n = n;
+  HIP_OK(h.alloc(n + 1));
+  b.tree = h.p;
+  uint32_t hs[4] = {0, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+  HIP_OK(stats.put(hs, 4, s));
+  HIP_OK(pv::launch_trie_build_lcp(b, stats.p, mb, s));
+  HIP_OK(hipMemcpyAsync(hs, stats.p, 16, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (const int rc = lcp_refusal(hs)) return rc;
+  // count, scan, write
+  pv::TuCtx c{};
+  c.blob = st.blob;
+  c.beg = st.beg;
+  c.end = st.end;
+  c.dig = st.dig;
+  c.table = st.table;
+  c.slots = st.slots;
+  c.n_nodes = (uint32_t)st.n_nodes;
+  uint32_t rw[8];
+  memcpy(rw, old_root, 32);
+  HIP_OK(droot.put(rw, 8, s));
+  c.root = droot.p;
+  c.key_blob = kb;
+  c.key_off = ko;
+  c.val_blob = vb;
+  c.val_off = vo;
+  c.n = n;
+  c.h = h.p;
+  HIP_OK(sizes.alloc(3 * (n + 1)));
+  HIP_OK(hipMemsetAsync(sizes.p, 0, 3 * (n + 1) * 8, s));
+  c.cnt = sizes.p;
+  c.pbytes = sizes.p + (n + 1);
+  c.vbytes = sizes.p + 2 * (n + 1);
+  HIP_OK(status.alloc(n));
+  c.status = status.p;
+  HIP_OK(pv::launch_trie_update_count(c, mb, s));
+  std::vector<uint8_t> hstat(n);
+  HIP_OK(hipMemcpyAsync(hstat.data(), status.p, n, hipMemcpyDeviceToHost, s));
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(n + 1)));
+  HIP_OK(pv::launch_exclusive_scan(c.cnt, n + 1, d.scan.p, s));
+  HIP_OK(pv::launch_exclusive_scan(c.pbytes, n + 1, d.scan.p, s));
+  HIP_OK(pv::launch_exclusive_scan(c.vbytes, n + 1, d.scan.p, s));
+  uint64_t tot[3] = {0, 0, 0};   // items, path bytes, payload bytes
+  for (int k = 0; k < 3; ++k)
+    HIP_OK(hipMemcpyAsync(&tot[k], sizes.p + k * (n + 1) + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  for (uint64_t j = 0; j < n; ++j)
+    if (hstat[j] != pv::SP_OK)
+      return fail(PV_EINVAL,
+                  hstat[j] == pv::SP_NODE_MISSING
+                      ? "state update: key %llu: the root or a node on its path is not in the store (status %u)"
+                      : "state update: key %llu: a node on its path is not a well-formed trie node (status %u)",
+                  (unsigned long long)j, (unsigned)hstat[j]);
+  if (tot[0] < n || tot[0] > pv::TB_MAX_KEYS)
+    return fail(PV_EINVAL, "state update: %llu merged items, above the 2^28 of one build", (unsigned long long)tot[0]);
+  const uint64_t items = tot[0];
+  HIP_OK(ikey.alloc(tot[1] + 16));
+  HIP_OK(ival.alloc(tot[2] + 16));
+  HIP_OK(ikoff.alloc(items + 1));
+  HIP_OK(ivoff.alloc(items + 1));
+  HIP_OK(inib.alloc(items));
+  HIP_OK(ikind.alloc(items));
+  HIP_OK(hipMemsetAsync(ikey.p + tot[1], 0, 16, s));
+  HIP_OK(hipMemsetAsync(ival.p + tot[2], 0, 16, s));
+  HIP_OK(hipMemcpyAsync(ikoff.p + items, c.pbytes + n, 8, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(ivoff.p + items, c.vbytes + n, 8, hipMemcpyDeviceToDevice, s));
+  c.ikey = ikey.p;
+  c.ikoff = ikoff.p;
+  c.ival = ival.p;
+  c.ivoff = ivoff.p;
+  c.inib = inib.p;
+  c.ikind = ikind.p;
+  HIP_OK(pv::launch_trie_update_emit(c, mb, s));
+  return build_core(d, s, ikey.p, ikoff.p, ival.p, ivoff.p, items, insert ? &st : nullptr, root, n_nodes, n_bytes,
+                    node_blob, blob_cap, node_off, node_cap, digests, host_out, inib.p, ikind.p);
+}
+
+// n == 0: the root stays, no node, no launch for the update; every output that is given is
+// written, and, as with the empty build, neither the store nor an input buffer is looked at
+int update_empty(Entry& en, void* stream, const uint8_t* old_root, uint8_t* new_root, uint64_t* n_nodes,
+                 uint64_t* n_bytes, uint64_t* node_off, bool host_out) {
+  if (new_root && old_root) memcpy(new_root, old_root, 32);
+  return build_empty(en, stream, nullptr, n_nodes, n_bytes, node_off, host_out);
+}
+
+}  // namespace
+
+extern "C" {
+
+// A 3PC batch of PruningState.set onto the state at a committed root, and the new headHash
+// (state/pruning_state.py:60-61, 136; Trie.update, state/trie/pruning_trie.py:1006-1027), as one
+// batch over device buffers; see include/plenum_verify.h.
+int pv_state_update_device(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                           const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert,
+                           uint8_t* new_root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
+                           uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, void* stream) {
+  Entry en;
+  if (n == 0) {   // as the empty build: nothing is looked at, the store included
+    if (const int rc = en.check()) return rc;
+    return update_empty(en, stream, old_root, new_root, n_nodes, n_bytes, node_off, false);
+  }
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (!old_root || !new_root) return fail(PV_EINVAL, "null pointer");
+  if (!key_blob || !key_off || !val_blob || !val_off) return fail(PV_EINVAL, "null device buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  if ((reinterpret_cast<uintptr_t>(key_blob) & 3u) || (reinterpret_cast<uintptr_t>(val_blob) & 3u))
+    return fail(PV_EINVAL, "key_blob and val_blob must be 4-byte aligned");
+  if (digests && misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  return update_core(*en.d, en.s, *st, old_root, key_blob, key_off, val_blob, val_off, n, insert != 0, new_root,
+                     n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap, digests, false);
+}
+
+// The host form of the same (state/pruning_state.py:60-61; state/trie/pruning_trie.py:1006-1027):
+// keys in any order, the last of equal keys wins, as a sequence of sets gives.
+int pv_state_update(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                    const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                    uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                    uint64_t node_cap, uint8_t* digests) {
+  if (n == 0) {
+    Entry en;
+    if (const int rc = en.check()) return rc;
+    return update_empty(en, nullptr, old_root, new_root, n_nodes, n_bytes, node_off, true);
+  }
+  // checks and the sorted copy before the library lock, as pv_state_build
+  if (!old_root || !new_root) return fail(PV_EINVAL, "null pointer");
+  std::vector<uint64_t> ko, vo;
+  std::vector<uint8_t> kb, vb;
+  if (const int rc = sorted_pairs(key_blob, key_off, val_blob, val_off, n, ko, vo, kb, vb)) return rc;
+  const uint64_t m = ko.size() - 1;
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> dkb, dvb;
+  TmpBuf<uint64_t> dko, dvo;
+  StreamDrain tail{s};
+  HIP_OK(dkb.put(kb.data(), kb.size(), s));
+  HIP_OK(dvb.put(vb.data(), vb.size(), s));
+  HIP_OK(dko.put(ko.data(), m + 1, s));
+  HIP_OK(dvo.put(vo.data(), m + 1, s));
+  return update_core(*en.d, s, *st, old_root, dkb.p, dko.p, dvb.p, dvo.p, m, insert != 0, new_root, n_nodes, n_bytes,
+                     node_blob, blob_cap, node_off, node_cap, digests, true);
 }
 
 }  // extern "C"

@@ -242,6 +242,13 @@ hipError_t launch_trie_build_struct(const TbCtx& c, uint32_t* root_e, int max_bl
 hipError_t launch_trie_build_size(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s);
 hipError_t launch_trie_build_emit(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s);
 
+// Sets onto a committed root (pv_trie_update.h); all device memory.  tu_walk over the batch
+// keys, one key per lane: count mode (status[j], cnt / pbytes / vbytes [j]), then, after the
+// three scans, write mode (the merged items).
+struct TuCtx;
+hipError_t launch_trie_update_count(const TuCtx& c, int max_blocks, hipStream_t s);
+hipError_t launch_trie_update_emit(const TuCtx& c, int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

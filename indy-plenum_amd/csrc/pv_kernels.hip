@@ -20,6 +20,7 @@
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
 #include "pv_trie_build.h"
+#include "pv_trie_update.h"
 #include "pv_kernels.h"
 #include "plenum_verify.h"
 
@@ -2001,6 +2002,32 @@ hipError_t launch_trie_build_size(const TbCtx& c, uint32_t lv, int max_blocks, h
 hipError_t launch_trie_build_emit(const TbCtx& c, uint32_t lv, int max_blocks, hipStream_t s) {
   if (c.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_trie_build_emit, dim3(mp_grid(3 * c.n, max_blocks)), dim3(256), 0, s, c, lv);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- sets onto a committed root
+// pv_trie_update.h: one batch key per lane walks the old trie; lanes of a wave
+// diverge in trip count only.  No atomics: each lane writes its own entries.
+__global__ __launch_bounds__(256) void k_trie_update_count(TuCtx c) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < c.n; j += stride)
+    c.status[j] = (uint8_t)tu_walk(c, j, false);
+}
+
+__global__ __launch_bounds__(256) void k_trie_update_emit(TuCtx c) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < c.n; j += stride) (void)tu_walk(c, j, true);
+}
+
+hipError_t launch_trie_update_count(const TuCtx& c, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_update_count, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_update_emit(const TuCtx& c, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_update_emit, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c);
   return hipGetLastError();
 }
 

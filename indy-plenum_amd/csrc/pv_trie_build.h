@@ -50,6 +50,16 @@
 // The blob keeps the over-read contract of pv_sha3.h: 4-byte aligned base and
 // 16 readable bytes after the last node.
 //
+// A merged item list (pv_trie_update.h) instead of plain keys: with knib set,
+// path i has knib[i] nibbles (any parity; an odd path ends in a zero pad nibble)
+// and tb_lcp_one compares by nibble; with kind set, kind[i] == 1 marks a carried
+// child reference.  Such an item is never a branch value and a prefix of no
+// other path (tb_lcp_one refuses it).  Its entity 3 i + 2 is, with no nibble left
+// below its slot, the reference itself: elen is the reference's length, nothing
+// is emitted or hashed and tb_put_ref copies the payload bytes; with nibbles left
+// it is an extension node over them with the payload as its second item.  With
+// both null every routine does what it did for plain keys.
+//
 // The host twin is these routines called in index order.
 #pragma once
 #include <stdint.h>
@@ -87,6 +97,9 @@ struct TbCtx {
   uint8_t* out_blob;
   uint64_t* node_off;
   uint32_t* dig;           // 8 words per emitted node
+  // A merged item list (pv_trie_update.h) instead of plain keys; both null for a plain build.
+  const uint32_t* knib;    // n: the nibble length of path i (an odd path ends in a zero pad nibble); null: 2 per byte
+  const uint8_t* kind;     // n: 1 = the value of item i is a child reference carried as it is (TU_SUBTREE); null: none
 };
 
 // number of tree levels over n keys and their offsets (lvoff[0 .. nlv]); the words of the whole tree
@@ -103,7 +116,15 @@ inline uint32_t tb_tree_layout(uint64_t n, uint64_t lvoff[TB_MAX_LEVELS + 1]) {
   return k;
 }
 
-PV_HD uint64_t tb_knib(const TbCtx& c, uint64_t i) { return 2 * (c.key_off[i + 1] - c.key_off[i]); }
+PV_HD uint64_t tb_knib(const TbCtx& c, uint64_t i) {
+  return c.knib ? c.knib[i] : 2 * (c.key_off[i + 1] - c.key_off[i]);
+}
+
+// item i is a carried child reference
+PV_HD bool tb_subtree(const TbCtx& c, uint64_t i) { return c.kind && c.kind[i] == 1; }
+
+// entity e is a carried reference with no nibble left below its slot: the reference itself, no node
+PV_HD bool tb_is_ref(const TbCtx& c, uint32_t e) { return c.kind && e % 3 == 2 && c.aux[e] != 0; }
 
 // h[i], 0 <= i <= n, with the order check of the pair (i - 1, i) and the checks of value i
 PV_HD uint32_t tb_lcp_one(const TbCtx& c, uint64_t i, uint32_t& bad) {
@@ -111,7 +132,7 @@ PV_HD uint32_t tb_lcp_one(const TbCtx& c, uint64_t i, uint32_t& bad) {
   if (i < c.n) {
     const uint64_t a = c.val_off[i], b = c.val_off[i + 1];
     if (b < a) bad |= TB_BAD_OFFSET;
-    else if (b == a || b - a > TB_MAX_VAL_BYTES) bad |= TB_BAD_VALUE;
+    else if (b == a || b - a > TB_MAX_VAL_BYTES || (tb_subtree(c, i) && b - a > 33)) bad |= TB_BAD_VALUE;
     const uint64_t ka = c.key_off[i], kb = c.key_off[i + 1];
     if (kb < ka || kb - ka > TB_MAX_KEY_BYTES) bad |= TB_BAD_OFFSET;
   }
@@ -122,6 +143,21 @@ PV_HD uint32_t tb_lcp_one(const TbCtx& c, uint64_t i, uint32_t& bad) {
     return 1;
   }
   const uint8_t *a = c.key_blob + o0, *b = c.key_blob + o1;
+  if (c.knib) {   // paths of any parity, compared by nibble; a carried reference is a prefix of nothing
+    const uint64_t na = c.knib[i - 1], nb = c.knib[i], nm = na < nb ? na : nb;
+    if (na > 2 * (o1 - o0) || nb > 2 * (o2 - o1)) {
+      bad |= TB_BAD_OFFSET;
+      return 1;
+    }
+    uint64_t x = 0;
+    while (x < nm && sp_nibble(a, x) == sp_nibble(b, x)) ++x;
+    if (x == nm) {
+      if (na >= nb || tb_subtree(c, i - 1)) bad |= TB_BAD_ORDER;
+    } else if (sp_nibble(a, x) > sp_nibble(b, x)) {
+      bad |= TB_BAD_ORDER;
+    }
+    return (uint32_t)(x + 1);
+  }
   const uint64_t la = o1 - o0, lb = o2 - o1, m = la < lb ? la : lb;
   uint64_t k = 0;
   while (k < m && a[k] == b[k]) ++k;
@@ -276,7 +312,7 @@ PV_HD uint32_t tb_struct_one(const TbCtx& c, uint64_t i) {
   c.lvl[e0 + 2] = ll;
   c.aux[e0] = ae;
   c.aux[e0 + 1] = ab;
-  c.aux[e0 + 2] = 0;
+  c.aux[e0 + 2] = (ll != TB_VOID && tb_subtree(c, i) && tb_knib(c, i) == ll) ? 1u : 0u;
   return root;
 }
 
@@ -335,6 +371,11 @@ PV_HD uint8_t* tb_put_ref(const TbCtx& c, uint8_t* w, uint32_t ch) {
     return w;
   }
   const uint32_t e = ch - 1, l = c.elen[e];
+  if (tb_is_ref(c, e)) {   // the carried bytes: 0xa0 and a hash, or an inline node
+    const uint8_t* s = c.val_blob + c.val_off[e / 3];
+    for (uint32_t k = 0; k < l && k < 33; ++k) *w++ = s[k];
+    return w;
+  }
   if (l >= 32) {
     *w++ = 0xa0;
     const uint32_t* d = c.dig + 8 * c.idx[e];
@@ -359,6 +400,7 @@ PV_HD uint64_t tb_payload(const TbCtx& c, uint32_t e) {
   const uint32_t k = e - 3 * (uint32_t)i;
   if (k == 2) {
     const uint64_t vo = c.val_off[i];
+    if (tb_subtree(c, i)) return tb_hp_len(c.lvl[e], tb_knib(c, i)) + (c.val_off[i + 1] - vo);   // an extension
     return tb_hp_len(c.lvl[e], tb_knib(c, i)) + tb_str_len(c.val_blob + vo, c.val_off[i + 1] - vo);
   }
   if (k == 0) return tb_hp_len(c.lvl[e], c.tree[i] - 1) + tb_ref_len(c, e + 2);
@@ -372,6 +414,11 @@ PV_HD uint64_t tb_payload(const TbCtx& c, uint32_t e) {
 
 // size pass: entity e (lvl[e] != TB_VOID, its children sized)
 PV_HD void tb_size_one(const TbCtx& c, uint32_t e) {
+  if (tb_is_ref(c, e)) {   // no node: its parent copies the reference, nothing is emitted
+    const uint64_t i = e / 3;
+    c.elen[e] = (uint32_t)(c.val_off[i + 1] - c.val_off[i]);
+    return;
+  }
   const uint64_t body = tb_payload(c, e);
   const uint64_t len = rlp_list_header_len(body) + body;
   const bool emit = len >= 32 || e == *c.root_e;
@@ -382,6 +429,7 @@ PV_HD void tb_size_one(const TbCtx& c, uint32_t e) {
 
 // write pass: entity e (its children written and hashed, off and idx scanned)
 PV_HD void tb_emit_one(const TbCtx& c, uint32_t e) {
+  if (tb_is_ref(c, e)) return;
   const uint64_t i = e / 3;
   const uint32_t k = e - 3 * (uint32_t)i;
   const uint32_t len = c.elen[e];
@@ -396,8 +444,14 @@ PV_HD void tb_emit_one(const TbCtx& c, uint32_t e) {
   uint8_t* w = tb_put_hdr(dst, 192, len - hl);
   if (k == 2) {
     const uint64_t vo = c.val_off[i];
-    w = tb_put_hp(w, c.key_blob + c.key_off[i], c.lvl[e], tb_knib(c, i), true);
-    w = tb_put_str(w, c.val_blob + vo, c.val_off[i + 1] - vo);
+    const bool sub = tb_subtree(c, i);
+    w = tb_put_hp(w, c.key_blob + c.key_off[i], c.lvl[e], tb_knib(c, i), !sub);
+    if (sub) {
+      const uint64_t vl = c.val_off[i + 1] - vo;
+      for (uint64_t t = 0; t < vl && t < 33; ++t) *w++ = c.val_blob[vo + t];
+    } else {
+      w = tb_put_str(w, c.val_blob + vo, c.val_off[i + 1] - vo);
+    }
   } else if (k == 0) {
     w = tb_put_hp(w, c.key_blob + c.key_off[c.aux[e]], c.lvl[e], c.tree[i] - 1, false);
     w = tb_put_ref(c, w, e + 2);

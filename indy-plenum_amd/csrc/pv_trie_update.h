@@ -1,0 +1,348 @@
+// Sets applied to a committed root, shared by device and host: the merge in
+// front of pv_trie_build.h.  The reference applies a 3PC batch with one
+// PruningState.set per key (state/pruning_state.py:60-61 -> Trie.update,
+// state/trie/pruning_trie.py:1006-1027), each rewriting the path from the root
+// to one leaf.  Here the batch is one computation: the old trie at root R (in a
+// resident store, pv_trie_store.h) and n sorted batch keys are merged into one
+// sorted list of ITEMS, and the builder runs over that list.
+//
+// Items.  A nibble path of any parity and a payload.  TU_VALUE: the payload is
+// a value as the trie stores it.  TU_SUBTREE: the payload is a child reference
+// of the old trie kept as it is (0xa0 + 32 hash bytes, or the RLP of an inline
+// node under 32 bytes): a whole subtree no batch key enters, which the builder
+// puts back without looking inside.
+//
+// The walk.  One lane per batch key K_j walks from R as sg_walk does (hashed
+// children through ts_find, inline children in place) and carries what it
+// passes.  h[j] = 1 + LCP(K_{j-1}, K_j) in nibbles (h[0] = h[n] = 0, from
+// tb_lcp_one over the batch).  At a node that starts at depth D, `first` means
+// h[j] <= D (the previous key is not in the run of keys that visit this node)
+// and `last` means h[j + 1] <= D.
+//   Branch.  Its value, if `first` and len(K_j) != D, goes BEFORE.  With
+//   s = K_j[D] (-1 at the key's end) and s_prev = K_{j-1}[D] (-1 if `first` or
+//   K_{j-1} ends here), the non-blank slots s_prev < t < s go BEFORE, and, if
+//   `last`, the non-blank slots t > s go AFTER.  The walk descends into slot s.
+//   Leaf or extension with path P, Q = K_j[:D] + P.  A leaf with Q == K_j is
+//   overwritten; an extension with Q a prefix of K_j is dissolved (the walk
+//   goes on below it).  Otherwise the leaf's value or the extension's child
+//   reference is an item at path Q: BEFORE if Q < K_j and (`first`, or
+//   K_{j-1} < Q without K_{j-1} absorbing Q, see tu_cmp); AFTER if `last` and
+//   Q > K_j.
+// The lane's output is its BEFORE items in walk order, VALUE(K_j), then its
+// AFTER groups, deepest node first.  Concatenated in key order this is strictly
+// increasing and prefix-consistent with no sort and no atomic: the order is
+// fixed by the inputs alone.
+//
+// Two passes.  tu_walk in count mode gives each key its number of items, path
+// bytes and payload bytes; three exclusive scans give each key its ranges; the
+// write mode walks again and fills them.  An AFTER group is placed from the
+// range's end backwards (its size is known from the node alone), so the deepest
+// group ends up first without a stack.
+//
+// Bounds.  Every loop is bounded by a key length, a path length checked against
+// its node, 17 items or 33 reference bytes; no length is read before it is
+// checked against the enclosing node; no lane keeps an array it indexes at run
+// time.  A missing or malformed node gives the key a PV_SP_* status and the
+// caller refuses the whole call.
+//
+// The host twin is tu_walk called in index order.
+#pragma once
+#include <stdint.h>
+
+#include "pv_trie_store.h"
+
+namespace pv {
+
+enum : uint8_t { TU_VALUE = 0, TU_SUBTREE = 1 };
+
+struct TuCtx {
+  // the store that holds the old trie
+  const uint8_t* blob;
+  const uint64_t *beg, *end;
+  const uint32_t *dig, *table;
+  uint32_t slots, n_nodes;
+  const uint32_t* root;   // 8 words, not the blank root
+  // the batch: sorted distinct keys, non-empty values (checked by tb_lcp_one before)
+  const uint8_t* key_blob;
+  const uint64_t* key_off;
+  const uint8_t* val_blob;
+  const uint64_t* val_off;
+  uint64_t n;
+  const uint32_t* h;      // n + 1
+  // per key, n + 1 entries: sizes from the count mode, scanned to range starts
+  uint64_t *cnt, *pbytes, *vbytes;
+  uint8_t* status;        // n
+  // the merged items (write mode)
+  uint8_t* ikey;
+  uint64_t* ikoff;
+  uint8_t* ival;
+  uint64_t* ivoff;
+  uint32_t* inib;
+  uint8_t* ikind;
+};
+
+struct TuCur {
+  uint64_t i, k, v;   // item index, path byte offset, payload byte offset (count mode: sizes)
+};
+
+// A child reference item [start, ie) with payload [ib, ie): SP_OK and ref_len =
+// 0 (blank) or the bytes to carry from `start`; hashed = a 32-byte hash.
+PV_HD uint32_t tu_ref(uint64_t start, bool il, uint64_t ib, uint64_t ie, uint64_t& ref_len, bool& hashed) {
+  ref_len = 0;
+  hashed = false;
+  if (il) {
+    if (ie - start >= 32) return SP_MALFORMED;
+    ref_len = ie - start;
+    return SP_OK;
+  }
+  if (ie == ib) return SP_OK;
+  if (ie - ib != 32 || ib != start + 1) return SP_NODE_MISSING;
+  ref_len = 33;
+  hashed = true;
+  return SP_OK;
+}
+
+// Q = X[:D] + path (pn nibbles of the hex-prefix bytes p from nibble `skip`)
+// against X (xn >= D nibbles).  0: equal; 1: Q a proper prefix of X; 2: X a
+// proper prefix of Q; 3: Q < X at a nibble; 4: X < Q at a nibble.  X absorbs a
+// leaf's Q on 0 and an extension's Q on 0 or 1; X < Q without absorbing is 2 or 4.
+PV_HD uint32_t tu_cmp(const uint8_t* p, uint64_t skip, uint64_t pn, const uint8_t* x, uint64_t D, uint64_t xn) {
+  const uint64_t rest = xn - D, m = pn < rest ? pn : rest;
+  uint64_t i = 0;
+  uint32_t a = 0, b = 0;
+  for (; i < m; ++i) {
+    a = sp_nibble(p, skip + i);
+    b = sp_nibble(x, D + i);
+    if (a != b) break;
+  }
+  if (i == pn) return i == rest ? 0u : 1u;
+  if (i == rest) return 2u;
+  return a < b ? 3u : 4u;
+}
+
+// One item at `at`: the path is key[:D] followed by the nibble `slot` (< 16) or
+// by pn path nibbles of p; the payload is src[0 .. len).  Count mode (!write)
+// only advances `at`.
+PV_HD void tu_put(const TuCtx& c, bool write, TuCur& at, const uint8_t* key, uint64_t D, const uint8_t* p,
+                  uint64_t skip, uint64_t pn, uint32_t slot, uint8_t kind, const uint8_t* src, uint64_t len) {
+  const uint64_t nib = D + (slot < 16 ? 1 : pn), nb = (nib + 1) / 2;
+  if (write) {
+    uint8_t* w = c.ikey + at.k;
+    for (uint64_t b = 0; b < nb; ++b) {
+      uint32_t v = 0;
+      for (uint32_t half = 0; half < 2; ++half) {
+        const uint64_t x = 2 * b + half;
+        uint32_t q = 0;   // the pad nibble of an odd path
+        if (x < D) q = sp_nibble(key, x);
+        else if (x < nib) q = slot < 16 ? slot : sp_nibble(p, skip + (x - D));
+        v = 16 * v + q;
+      }
+      w[b] = (uint8_t)v;
+    }
+    uint8_t* o = c.ival + at.v;
+    for (uint64_t t = 0; t < len; ++t) o[t] = src[t];
+    c.ikoff[at.i] = at.k;
+    c.ivoff[at.i] = at.v;
+    c.inib[at.i] = (uint32_t)nib;
+    c.ikind[at.i] = kind;
+  }
+  at.i += 1;
+  at.k += nb;
+  at.v += len;
+}
+
+// The walk of batch key j.  Count mode: cnt / pbytes / vbytes [j] and status[j].
+// Write mode (after the scans, every status SP_OK): the items of key j.
+PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) {
+  const uint8_t* key = c.key_blob + c.key_off[j];
+  const uint64_t knib = 2 * (c.key_off[j + 1] - c.key_off[j]);
+  const uint32_t hl = c.h[j], hr = c.h[j + 1];
+  const uint8_t* kp = key;
+  uint64_t pnib = 0;
+  if (j > 0) {
+    kp = c.key_blob + c.key_off[j - 1];
+    pnib = 2 * (c.key_off[j] - c.key_off[j - 1]);
+  }
+  TuCur front{0, 0, 0}, back{0, 0, 0};
+  if (write) {
+    front = TuCur{c.cnt[j], c.pbytes[j], c.vbytes[j]};
+    back = TuCur{c.cnt[j + 1], c.pbytes[j + 1], c.vbytes[j + 1]};
+  }
+  const uint8_t* blob = c.blob;
+  uint32_t id = ts_find(c.table, c.slots, c.dig, c.n_nodes, c.root);
+  if (id == TS_ABSENT) return SP_NODE_MISSING;
+  uint64_t cb = c.beg[id], ce = c.end[id], D = 0;
+  uint32_t st = SP_MALFORMED;   // the step bound ran out
+  for (uint64_t step = 0; step <= knib; ++step) {
+    bool is_list;
+    uint64_t pb, pe;
+    if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) break;
+    const bool first = hl <= D, last = hr <= D;
+    const int32_t s = D < knib ? (int32_t)sp_nibble(key, D) : -1;
+    const int32_t s_prev = (!first && D < pnib) ? (int32_t)sp_nibble(kp, D) : -1;
+    // first scan: the shape, item 0 and 1, slot s, item 16, the AFTER group's size
+    uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0, sls = 0, slb = 0, sle = 0, vb = 0, ve = 0;
+    bool i0l = false, i1l = false, sll = false, vl = false;
+    uint32_t count = 0, bad = SP_OK;
+    TuCur grp{0, 0, 0};
+    uint64_t pos = pb;
+    while (pos < pe) {
+      bool il;
+      uint64_t ib, ie;
+      if (count == 17 || !rlp_item(blob, pos, pe, il, ib, ie)) {
+        bad = SP_MALFORMED;
+        break;
+      }
+      if (count == 0) i0b = ib, i0e = ie, i0l = il;
+      if (count == 1) i1s = pos, i1b = ib, i1e = ie, i1l = il;
+      if ((int32_t)count == s) sls = pos, slb = ib, sle = ie, sll = il;
+      if (count == 16) vb = ib, ve = ie, vl = il;
+      pos = ie;
+      ++count;
+    }
+    if (bad != SP_OK || (count != 17 && count != 2)) break;
+    uint64_t rs, rb, re;   // the child the walk goes on in
+    bool rl;
+    if (count == 17) {
+      if (vl) break;
+      // second scan: the carried slots, checked; in write mode also written
+      if (ve > vb && first && knib != D) tu_put(c, write, front, key, D, key, 0, 0, 16, TU_VALUE, blob + vb, ve - vb);
+      for (uint32_t pass = 0; pass < 2 && bad == SP_OK; ++pass) {
+        // pass 0 sizes the AFTER group (and counts BEFORE in count mode); pass 1 writes
+        if (pass == 1 && !write) break;
+        TuCur w = back;
+        if (pass == 1) {
+          back.i -= grp.i, back.k -= grp.k, back.v -= grp.v;
+          w = back;
+        }
+        pos = pb;
+        for (int32_t t = 0; t < 16; ++t) {
+          bool il;
+          uint64_t ib, ie, rlen;
+          bool hashed;
+          if (!rlp_item(blob, pos, pe, il, ib, ie)) {   // parsed by the first scan: never
+            bad = SP_MALFORMED;
+            break;
+          }
+          const bool before = t > s_prev && t < s, after = last && t > s;
+          if (before || after) {
+            const uint32_t r = tu_ref(pos, il, ib, ie, rlen, hashed);
+            if (r != SP_OK) {
+              bad = r;
+              break;
+            }
+            if (rlen) {
+              if (pass == 0) {
+                if (after) tu_put(c, false, grp, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
+                else if (!write) tu_put(c, false, front, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
+              } else {
+                tu_put(c, true, before ? front : w, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
+              }
+            }
+          }
+          pos = ie;
+        }
+      }
+      if (bad != SP_OK) {
+        st = bad;
+        break;
+      }
+      if (!write) front.i += grp.i, front.k += grp.k, front.v += grp.v;
+      if (s < 0) {
+        st = SP_OK;
+        break;
+      }
+      rs = sls, rb = slb, re = sle, rl = sll;
+      D += 1;
+    } else {
+      if (i0l || i0e == i0b) break;
+      const uint8_t* p = blob + i0b;
+      const uint32_t flags = p[0] >> 4, odd = flags & 1u;
+      const uint64_t pn = 2 * (i0e - i0b - 1) + odd, skip = 2 - odd;
+      const bool leaf = (flags & 2u) != 0;
+      if (!leaf && pn == 0) break;
+      if (leaf && (i1l || i1e == i1b)) break;
+      const uint32_t cq = tu_cmp(p, skip, pn, key, D, knib);
+      if (leaf && cq == 0) {   // overwritten
+        st = SP_OK;
+        break;
+      }
+      if (!leaf && cq <= 1) {   // dissolved
+        rs = i1s, rb = i1b, re = i1e, rl = i1l;
+        D += pn;
+      } else {
+        const uint8_t* src = blob + i1b;
+        uint64_t len = i1e - i1b;
+        if (!leaf) {
+          bool hashed;
+          const uint32_t r = tu_ref(i1s, i1l, i1b, i1e, len, hashed);
+          if (r != SP_OK || len == 0) {
+            st = r != SP_OK ? r : (uint32_t)SP_MALFORMED;
+            break;
+          }
+          src = blob + i1s;
+        }
+        const uint8_t kind = leaf ? TU_VALUE : TU_SUBTREE;
+        if (cq == 1 || cq == 3) {
+          bool mine = first;
+          if (!mine) {
+            const uint32_t cp = tu_cmp(p, skip, pn, kp, D, pnib);
+            mine = cp == 2 || cp == 4;
+          }
+          if (mine) tu_put(c, write, front, key, D, p, skip, pn, 16, kind, src, len);
+        } else if (last) {
+          if (write) {
+            TuCur one{0, 0, 0};
+            tu_put(c, false, one, key, D, p, skip, pn, 16, kind, src, len);
+            back.i -= one.i, back.k -= one.k, back.v -= one.v;
+            TuCur w = back;
+            tu_put(c, true, w, key, D, p, skip, pn, 16, kind, src, len);
+          } else {
+            tu_put(c, false, front, key, D, p, skip, pn, 16, kind, src, len);
+          }
+        }
+        st = SP_OK;
+        break;
+      }
+    }
+    uint64_t rlen;
+    bool hashed;
+    const uint32_t r = tu_ref(rs, rl, rb, re, rlen, hashed);
+    if (r != SP_OK) {
+      st = r;
+      break;
+    }
+    if (rlen == 0) {   // a blank slot ends the walk; an extension over nothing is no node
+      st = count == 17 ? (uint32_t)SP_OK : (uint32_t)SP_MALFORMED;
+      break;
+    }
+    if (!hashed) {
+      cb = rs;
+      ce = re;
+      continue;
+    }
+    uint32_t t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const uint8_t* q = blob + rb + 4 * k;
+      t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    }
+    id = ts_find(c.table, c.slots, c.dig, c.n_nodes, t);
+    if (id == TS_ABSENT) {
+      st = SP_NODE_MISSING;
+      break;
+    }
+    cb = c.beg[id];
+    ce = c.end[id];
+  }
+  if (st != SP_OK) return st;
+  tu_put(c, write, front, key, knib, key, 0, 0, 16, TU_VALUE, c.val_blob + c.val_off[j], c.val_off[j + 1] - c.val_off[j]);
+  if (!write) {
+    c.cnt[j] = front.i;
+    c.pbytes[j] = front.k;
+    c.vbytes[j] = front.v;
+  }
+  return SP_OK;
+}
+
+}  // namespace pv

@@ -114,6 +114,15 @@ SIGNATURES = [
     ('pv_state_build_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64),
       ctypes.POINTER(ctypes.c_uint64), _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, ctypes.c_int, _vp]),
+    # old_root, new_root: 32 bytes of HOST memory in both forms
+    ('pv_state_update', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
+      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp]),
+    ('pv_state_update_device', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
+      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_state_store_prove', ctypes.c_int,
      [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
       _vp, ctypes.c_uint64]),

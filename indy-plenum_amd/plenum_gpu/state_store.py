@@ -38,8 +38,13 @@ reference would return [b''].
   PruningState.set per pair (state/pruning_state.py:60-61, Trie.update,
   state/trie/pruning_trie.py:1006-1027); `build_host(items)` is its pure-Python mirror.
 
+* `GpuStateStore.update_state(root, items)` -- pv_state_update: one 3PC batch of sets applied to
+  the state at a committed root (csrc/pv_trie_update.h): one lane per batch key walks the old trie in
+  the store and carries the children no batch key enters as they are, and the build runs over the
+  merged list; `update_host(db, root, items)` is its pure-Python mirror over a {hash: RLP} dict.
+
 Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal),
-deletion and pruning of nodes, applying sets to an existing root on the device.
+deletion and pruning of nodes.
 """
 import ctypes
 import hashlib
@@ -257,6 +262,258 @@ def build_host(items):
     return build_encoded_host(_pairs(items))
 
 
+# ------------------------------------------------------------------ sets onto a committed root
+ITEM_VALUE, ITEM_SUBTREE = 0, 1   # csrc/pv_trie_update.h: TU_VALUE, TU_SUBTREE
+
+
+class _Raw(bytes):
+    """RLP that is already encoded: a child reference carried as it is"""
+
+
+def _rlp_raw(item):
+    if isinstance(item, _Raw):
+        return bytes(item)
+    if isinstance(item, (list, tuple)):
+        body = b''.join(_rlp_raw(x) for x in item)
+        return _length_prefix(len(body), 192) + body
+    return rlp_encode(item)
+
+
+def _node_fields(blob, cb, ce):
+    """the 2 or 17 items of the node RLP blob[cb:ce] -> [(start, is_list, payload begin, payload
+    end)], or None for anything else (tu_fields of csrc/pv_trie_update.h)"""
+    head = _rlp_item(blob, cb, ce)
+    if head is None or not head[0] or head[2] != ce:
+        return None
+    items, pos = [], head[1]
+    while pos < ce:
+        if len(items) == 17:
+            return None
+        it = _rlp_item(blob, pos, ce)
+        if it is None:
+            return None
+        items.append((pos,) + it)
+        pos = it[2]
+    return items if len(items) in (2, 17) else None
+
+
+def _child_ref(blob, it):
+    """a child reference -> (status, b'' for blank or the reference's bytes as they are): 0xa0 and
+    32 hash bytes, or the RLP of an inline node under 32 bytes"""
+    start, is_list, pb, pe = it
+    if is_list:
+        return (PV_SP_OK, bytes(blob[start:pe])) if pe - start < 32 else (PV_SP_MALFORMED, b'')
+    if pe == pb:
+        return PV_SP_OK, b''
+    if pe - pb != 32 or pb != start + 1:
+        return PV_SP_NODE_MISSING, b''
+    return PV_SP_OK, bytes(blob[start:pe])
+
+
+def _cmp_path(path, rest):
+    """Q = prefix + path against X = prefix + rest -> 0: equal, 1: Q a proper prefix of X, 2: X a
+    proper prefix of Q, 3: Q < X at a nibble, 4: X < Q at a nibble"""
+    m = 0
+    while m < len(path) and m < len(rest) and path[m] == rest[m]:
+        m += 1
+    if m == len(path):
+        return 0 if m == len(rest) else 1
+    if m == len(rest):
+        return 2
+    return 3 if path[m] < rest[m] else 4
+
+
+def _lcp(a, b):
+    m = 0
+    while m < len(a) and m < len(b) and a[m] == b[m]:
+        m += 1
+    return m
+
+
+def _merge_key(db, root, keys, j, value):
+    """The walk of batch key j (tu_walk of csrc/pv_trie_update.h) -> (status, its items in order):
+    the old trie's values and subtrees it carries before itself, its own VALUE, those after."""
+    k = keys[j]
+    kp = keys[j - 1] if j else None
+    lp = _lcp(kp, k) if j else -1
+    ln = _lcp(keys[j + 1], k) if j + 1 < len(keys) else -1
+    before, after = [], []
+    blob = db.get(root)
+    if blob is None:
+        return PV_SP_NODE_MISSING, []
+    cb, ce, depth = 0, len(blob), 0
+    for _ in range(len(k) + 1):
+        f = _node_fields(blob, cb, ce)
+        if f is None:
+            return PV_SP_MALFORMED, []
+        first, last = lp < depth, ln < depth
+        if len(f) == 17:
+            _, vl, vb, ve = f[16]
+            if vl:
+                return PV_SP_MALFORMED, []
+            if ve > vb and first and len(k) != depth:
+                before.append((k[:depth], ITEM_VALUE, bytes(blob[vb:ve])))
+            s = k[depth] if len(k) > depth else -1
+            s_prev = kp[depth] if not first and len(kp) > depth else -1
+            group = []
+            for t in list(range(s_prev + 1, s)) + (list(range(s + 1, 16)) if last else []):
+                st, ref = _child_ref(blob, f[t])
+                if st != PV_SP_OK:
+                    return st, []
+                if ref:
+                    (before if t < s else group).append((k[:depth] + [t], ITEM_SUBTREE, ref))
+            if group:
+                after.append(group)
+            if s < 0:
+                break
+            nxt = f[s]
+            depth += 1
+        else:
+            _, pl, pb, pe = f[0]
+            if pl or pe == pb:
+                return PV_SP_MALFORMED, []
+            flags = blob[pb] >> 4
+            odd, leaf = flags & 1, bool(flags & 2)
+            pn = 2 * (pe - pb - 1) + odd
+            if not leaf and pn == 0:
+                return PV_SP_MALFORMED, []
+            path = [_nibble(blob, pb, 2 - odd + i) for i in range(pn)]
+            c = _cmp_path(path, k[depth:])
+            if leaf:
+                _, vl, vb, ve = f[1]
+                if vl or ve == vb:
+                    return PV_SP_MALFORMED, []
+            if leaf and c == 0:
+                break                                   # overwritten
+            if not leaf and c in (0, 1):                # dissolved: its nibbles are the key's
+                nxt = f[1]
+                depth += pn
+            else:
+                if leaf:
+                    item = (k[:depth] + path, ITEM_VALUE, bytes(blob[vb:ve]))
+                else:
+                    st, ref = _child_ref(blob, f[1])
+                    if st != PV_SP_OK or not ref:
+                        return st or PV_SP_MALFORMED, []
+                    item = (k[:depth] + path, ITEM_SUBTREE, ref)
+                if c in (1, 3):
+                    if first or _cmp_path(path, kp[depth:]) in (2, 4):
+                        before.append(item)
+                elif last:
+                    after.append([item])
+                break
+        st, ref = _child_ref(blob, nxt)
+        if st != PV_SP_OK:
+            return st, []
+        if not ref:
+            if len(f) == 2:
+                return PV_SP_MALFORMED, []              # an extension over nothing
+            break
+        if nxt[1]:                                      # an inline node, walked in place
+            cb, ce = nxt[0], nxt[3]
+        else:
+            blob = db.get(ref[1:])
+            if blob is None:
+                return PV_SP_NODE_MISSING, []
+            cb, ce = 0, len(blob)
+    else:
+        return PV_SP_MALFORMED, []                      # the step bound ran out
+    return PV_SP_OK, before + [(k, ITEM_VALUE, value)] + [it for g in reversed(after) for it in g]
+
+
+def merge_host(db, root, pairs):
+    """The merge of csrc/pv_trie_update.h over `db` = {hash: node RLP}: the trie at `root` and
+    sorted distinct (key, encoded value) pairs -> (status, index of the first refused key,
+    [(nibbles, kind, payload)]), one strictly increasing list that holds every new value, every
+    old value outside the batch and, as a SUBTREE, the reference of every child no batch key
+    enters.  No sort: key j's items follow key j - 1's."""
+    keys = [[n for b in k for n in (b >> 4, b & 15)] for k, _ in pairs]
+    out = []
+    for j in range(len(pairs)):
+        st, items = _merge_key(db, root, keys, j, pairs[j][1])
+        if st != PV_SP_OK:
+            return st, j, []
+        out += items
+    return PV_SP_OK, 0, out
+
+
+def build_items_host(items):
+    """build_encoded_host over merged items [(nibbles, kind, payload)]: a SUBTREE item with no
+    nibble left below its slot is its payload, the reference itself; with nibbles left it is an
+    extension over them.  It is never a branch value.  -> (root, {hash: node RLP})"""
+    db = {}
+    keys = [it[0] for it in items]
+
+    def ref(node, root=False):
+        if isinstance(node, _Raw):
+            return node
+        enc = _rlp_raw(node)
+        if len(enc) < 32 and not root:
+            return _Raw(enc)
+        h = hashlib.sha3_256(enc).digest()
+        db[h] = enc
+        return h
+
+    def node_of(lo, hi, depth):
+        if hi - lo == 1:
+            _, kind, payload = items[lo]
+            if kind == ITEM_VALUE:
+                return [_hex_prefix(keys[lo][depth:], True), payload]
+            if len(keys[lo]) == depth:
+                return _Raw(payload)
+            return [_hex_prefix(keys[lo][depth:], False), _Raw(payload)]
+        first, last = keys[lo], keys[hi - 1]
+        d = depth
+        while d < len(first) and d < len(last) and first[d] == last[d]:
+            d += 1
+        if d > depth:
+            return [_hex_prefix(first[depth:d], False), ref(node_of(lo, hi, d))]
+        slots, value = [b''] * 16, b''
+        if len(first) == depth:
+            value = items[lo][2]
+            lo += 1
+        while lo < hi:
+            nib, end = keys[lo][depth], lo
+            while end < hi and keys[end][depth] == nib:
+                end += 1
+            slots[nib] = ref(node_of(lo, end, depth + 1))
+            lo = end
+        return slots + [value]
+
+    limit, need = sys.getrecursionlimit(), max(len(k) for k in keys) + 100
+    if limit < need:
+        sys.setrecursionlimit(need)
+    try:
+        return ref(node_of(0, len(items), 0), root=True), db
+    finally:
+        if limit < need:
+            sys.setrecursionlimit(limit)
+
+
+def update_encoded_host(db, root, pairs):
+    """pv_state_update in Python: sorted distinct (key, encoded value) pairs set into the trie at
+    `root`, whose nodes are in `db` = {hash: node RLP} -> (new root, {hash: node RLP} of the nodes
+    the update emits: every re-encoded node, none from inside an untouched subtree).  KeyError
+    when the root or a node on a batch key's path is not in db, ValueError for a malformed one."""
+    root = bytes(root)
+    if not pairs:
+        return root, {}
+    if root == BLANK_ROOT:
+        return build_encoded_host(pairs)
+    st, j, items = merge_host(db, root, pairs)
+    if st == PV_SP_NODE_MISSING:
+        raise KeyError('key {}: the root or a node on its path is not in the store'.format(j))
+    if st != PV_SP_OK:
+        raise ValueError('key {}: a node on its path is not a well-formed trie node'.format(j))
+    return build_items_host(items)
+
+
+def update_host(db, root, items):
+    """(key, raw value) pairs in any order, the last of equal keys wins, set into the trie at
+    `root` as PruningState.set does -> (new root, emitted nodes)"""
+    return update_encoded_host(db, root, _pairs(items))
+
+
 def _root_ptr(root):
     return root.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
@@ -285,6 +542,33 @@ def _build_gpu(pairs, store_id, want_nodes=False):
     dig = np.zeros((max(nn.value, 1), 32), np.uint8)
     nat._check('pv_state_build', call(blob, nb.value, off, nn.value, dig))
     return root.tobytes(), nn.value, nb.value, blob[:nb.value], off, dig[:nn.value]
+
+
+def _update_gpu(store_id, root, pairs, insert=True, want_nodes=False):
+    """pv_state_update over (key, encoded value) pairs -> (new root, n_nodes, n_bytes[, blob, off, digests]).
+    With want_nodes the sizing call computes only and the retry inserts, so nothing is inserted twice."""
+    nat.ensure_init()
+    lib = nat.load()
+    n = len(pairs)
+    kblob, koff = nat.pack_messages([k for k, _ in pairs])
+    vblob, voff = nat.pack_messages([v for _, v in pairs])
+    old = np.frombuffer(bytes(root), np.uint8).copy()
+    new = np.zeros(32, np.uint8)
+    nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(ins, blob, bcap, off, ncap, dig):
+        return lib.pv_state_update(store_id, _root_ptr(old), _p(kblob), _p(koff), _p(vblob), _p(voff), n, int(ins),
+                                   _root_ptr(new), ctypes.byref(nn), ctypes.byref(nb), _p(blob), bcap, _p(off), ncap,
+                                   _p(dig))
+    if not want_nodes:
+        nat._check('pv_state_update', call(insert, None, 0, None, 0, None))
+        return new.tobytes(), nn.value, nb.value
+    nat._check('pv_state_update', call(False, None, 0, None, 0, None))   # sizes
+    blob = np.zeros(max(nb.value, 1), np.uint8)
+    off = np.zeros(nn.value + 1, np.uint64)
+    dig = np.zeros((max(nn.value, 1), 32), np.uint8)
+    nat._check('pv_state_update', call(insert, blob, nb.value, off, nn.value, dig))
+    return new.tobytes(), nn.value, nb.value, blob[:nb.value], off, dig[:nn.value]
 
 
 def state_root_batch(items):
@@ -373,6 +657,21 @@ class GpuStateStore:
         nodes -> the root hash.  Afterwards generate_state_proof(key, root, ...) and
         get_for_root_hash_batch work at that root; no host trie is involved."""
         return _build_gpu(_pairs(items), self._id)[0]
+
+    def update_state(self, root, items):
+        """Set (key, raw value) pairs into the state at the committed `root` on the device
+        (pv_state_update) and insert the nodes the update emits -> the new root hash: one 3PC batch
+        of PruningState.set (state/pruning_state.py:60-61) and the new headHash, with rlp([v]) applied
+        to each value as set does.  `root` and every earlier root stay provable.  Always on the GPU:
+        the old trie's nodes live there.  KeyError when the root or a node on a key's path is not in
+        the store, ValueError for a node that is no trie node."""
+        try:
+            return _update_gpu(self._id, root_hash_of(root), _pairs(items))[0]
+        except nat.PlenumGpuError as exc:
+            text = str(exc)
+            if 'state update: key ' in text:
+                raise (KeyError if 'is not in the store' in text else ValueError)(text) from None
+            raise
 
     def add_serialized_proof(self, data):
         """Add the nodes of a serialized proof (rlp(list of nodes)) -> the number new to the store"""

@@ -31,7 +31,7 @@ struct Built {
 };
 
 inline int build(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
-                 uint64_t n, Built& out) {
+                 uint64_t n, Built& out, const uint32_t* knib = nullptr, const uint8_t* kind = nullptr) {
   out = Built();
   if (n == 0) {
     alignas(16) uint8_t blank[32] = {0x80};   // the message and the bytes the hash may read past it
@@ -49,6 +49,8 @@ inline int build(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t
   c.val_blob = val_blob;
   c.val_off = val_off;
   c.n = n;
+  c.knib = knib;   // a merged item list (stateupdate_host.h), else null
+  c.kind = kind;
   c.nlv = pv::tb_tree_layout(n, lvoff);
   c.lvoff = lvoff;
   std::vector<uint32_t> tree(lvoff[c.nlv]), child(16 * n, 0), lvl(3 * n), aux(3 * n), elen(3 * n, 0);
