@@ -438,9 +438,9 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
  * _generate_state_proof has (pf.append(root), and the NOTE at :1102), the rest of the reference's
  * order is Python set order.  Blank root: the proof is the empty list, the one byte 0xc0, which
  * is what verify accepts; the reference would serialize [b''].
- * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal), deletion and
- * pruning of nodes (building a trie from a batch: pv_state_build; sets onto a committed root:
- * pv_state_update). */
+ * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal) and pruning of
+ * nodes (building a trie from a batch: pv_state_build; sets onto a committed root:
+ * pv_state_update; sets and removals: pv_state_apply). */
 #define PV_SP_PATH_TOO_LONG 4
 int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t *store_out);
 int pv_state_store_add(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
@@ -500,8 +500,8 @@ int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const ui
  * At most 2^28 keys per call, keys of at most 2^20 bytes, values of at most 2^30 bytes.
  * The empty key is a key like any other (the reference accepts it).  Differences from the
  * reference: it also keeps the intermediate nodes of every update, here only the nodes reachable
- * from the final root exist.  Sets onto an existing root: pv_state_update below.  Out of scope:
- * deletion. */
+ * from the final root exist.  Sets onto an existing root: pv_state_update below; sets and
+ * removals: pv_state_apply. */
 int pv_state_build(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob, const uint64_t *val_off,
                    uint64_t n, int32_t store, uint8_t *root, uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob,
                    uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap, uint8_t *digests);
@@ -546,8 +546,9 @@ int pv_state_build_device(const uint8_t *key_blob, const uint64_t *key_off, cons
  *            HOST buffers, keys in any order, the last of equal keys wins.
  *   pv_state_update_device (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
  *            DEVICE buffers (node outputs too), keys strictly increasing, on the store's device.
- * Calls are synchronous and ordered on the store's stream (NULL = the library's).  Sets only.
- * Out of scope: deletion (a set of the empty value), pruning of nodes no root reaches. */
+ * Calls are synchronous and ordered on the store's stream (NULL = the library's).  Sets only: an
+ * empty value is refused; removals go through pv_state_apply below.  Out of scope: pruning of
+ * nodes no root reaches. */
 int pv_state_update(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
                     const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
                     uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
@@ -556,6 +557,42 @@ int pv_state_update_device(int32_t store, const uint8_t *old_root, const uint8_t
                            const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert,
                            uint8_t *new_root, uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob,
                            uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap, uint8_t *digests, void *stream);
+
+/* Sets and removals applied to a committed root: pv_state_update with the third mutating call of
+ * the State interface, PruningState.remove (state/pruning_state.py:84-85; Trie.delete,
+ * state/trie/pruning_trie.py:683-848).  A pair with an EMPTY value removes its key (no set has an
+ * empty value: rlp([v]) has at least one byte); removing a key the state does not hold changes
+ * nothing.  The lane of a removed key walks and carries as a set's lane does, emits no value, and
+ * opens every child reference it carries from a branch on its path: a leaf child is carried as its
+ * path and value, an extension child as its path and child reference, a branch child as it is.  So
+ * a branch left with one entry collapses in the build over the merged list: a leaf or extension
+ * child merges its path with the slot nibble and any extension above, a branch child goes under a
+ * new or lengthened extension, a branch left with only its value becomes a leaf.
+ *   Arguments, outputs, capacities, insert, the sizing-call contract, n == 0 and the refusals are
+ *   those of pv_state_update[_device], except that an empty value is a removal, not a refusal.
+ *   The host form takes val_blob == NULL when no pair of the batch has a value byte.
+ *   No item left (every key of the state removed): new_root = SHA3-256(0x80), the blank root, zero
+ *   nodes, no build launch.  old_root the blank root: the removals are dropped and the rest is
+ *   pv_state_build.  A batch without removals gives the outputs of pv_state_update byte for byte.
+ *   Difference from the reference: it decodes the sibling of a removed key only when a collapse
+ *   happens; here a removal needs every node referenced from the branches on its path to be in
+ *   `store` (PV_EINVAL naming the key and PV_SP_NODE_MISSING otherwise; PV_SP_MALFORMED for a
+ *   referenced node that is no trie node).  A store that holds a whole state always has them; a
+ *   store filled from proofs alone may refuse a removal the reference would apply.
+ *   pv_state_apply (state/pruning_state.py:60-61, 84-85; pruning_trie.py:683-848, 1006-1027)
+ *            HOST buffers, keys in any order, the last of equal keys wins: a later removal beats
+ *            an earlier set and the other way round.
+ *   pv_state_apply_device (state/pruning_state.py:60-61, 84-85; pruning_trie.py:683-848, 1006-1027)
+ *            DEVICE buffers (node outputs too), keys strictly increasing, on the store's device.
+ * Out of scope: pruning of nodes no root reaches (the store only grows). */
+int pv_state_apply(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
+                   const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
+                   uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
+                   uint64_t node_cap, uint8_t *digests);
+int pv_state_apply_device(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
+                          const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
+                          uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap,
+                          uint64_t *node_off, uint64_t node_cap, uint8_t *digests, void *stream);
 
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of

@@ -3342,15 +3342,17 @@ bool key_less(const uint8_t* blob, const uint64_t* off, uint64_t a, uint64_t b, 
 // the last of equal keys kept, as blobs with 16 spare bytes and offsets from 0.
 int sorted_pairs(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
                  uint64_t n, std::vector<uint64_t>& ko, std::vector<uint64_t>& vo, std::vector<uint8_t>& kb,
-                 std::vector<uint8_t>& vb) {
-  if (!key_off || !val_off || !val_blob) return fail(PV_EINVAL, "null buffer");
+                 std::vector<uint8_t>& vb, bool empty_ok = false) {
+  if (!key_off || !val_off || (!val_blob && !empty_ok)) return fail(PV_EINVAL, "null buffer");
   if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
   Ragged keys(key_off, n), vals(val_off, n);
   if (const int rc = keys.check("key_off")) return rc;
   if (const int rc = vals.check("val_off")) return rc;
-  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
+  if ((keys.len && !key_blob) || (vals.len && !val_blob))   // a batch of removals alone has no value byte
+    return fail(PV_EINVAL, "null buffer");
   for (uint64_t i = 0; i < n; ++i) {
-    if (val_off[i + 1] == val_off[i]) return fail(PV_EINVAL, "value %llu is empty", (unsigned long long)i);
+    if (val_off[i + 1] == val_off[i] && !empty_ok)   // pv_state_apply: a removal
+      return fail(PV_EINVAL, "value %llu is empty", (unsigned long long)i);
     if (key_off[i + 1] - key_off[i] > pv::TB_MAX_KEY_BYTES || val_off[i + 1] - val_off[i] > pv::TB_MAX_VAL_BYTES)
       return fail(PV_EINVAL, "pair %llu: a key above 2^20 or a value above 2^30 bytes", (unsigned long long)i);
   }
@@ -3377,7 +3379,7 @@ int sorted_pairs(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t
   vb.assign(vo[m] + 16, 0);
   for (uint64_t k = 0; k < m; ++k) {
     if (ko[k + 1] > ko[k]) memcpy(&kb[ko[k]], key_blob + key_off[pick[k]], ko[k + 1] - ko[k]);
-    memcpy(&vb[vo[k]], val_blob + val_off[pick[k]], vo[k + 1] - vo[k]);
+    if (vo[k + 1] > vo[k]) memcpy(&vb[vo[k]], val_blob + val_off[pick[k]], vo[k + 1] - vo[k]);
   }
   return PV_OK;
 }
@@ -3453,16 +3455,77 @@ int pv_state_build(const uint8_t* key_blob, const uint64_t* key_off, const uint8
 // ------------------------------------------- sets onto a committed root
 namespace {
 
+// No item left: the blank root and no node (the outputs of build_empty, on the call's stream).
+int nothing_left(hipStream_t s, uint8_t* root, uint64_t* n_nodes, uint64_t* n_bytes, uint64_t* node_off, bool host_out) {
+  memcpy(root, kBlankRoot, 32);
+  if (n_nodes) *n_nodes = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (node_off) {
+    if (host_out) node_off[0] = 0;
+    else HIP_OK(hipMemsetAsync(node_off, 0, 8, s));
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  return PV_OK;
+}
+
+// A batch with removals onto the blank root: the removals are dropped and the rest is a build.
+// The batch has passed tb_lcp_one, so its offsets are monotone and bounded.  Not a hot path (a
+// ledger's first batch): the pairs are compacted on the host.
+int build_without_removals(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, const uint8_t* vb,
+                           const uint64_t* vo, uint64_t n, StateStore* st, uint8_t* root, uint64_t* n_nodes,
+                           uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                           uint64_t node_cap, uint8_t* digests, bool host_out) {
+  std::vector<uint64_t> hko(n + 1), hvo(n + 1);
+  HIP_OK(hipMemcpyAsync(hko.data(), ko, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(hvo.data(), vo, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  uint64_t kept = 0;
+  for (uint64_t i = 0; i < n; ++i) kept += hvo[i + 1] > hvo[i];
+  if (kept == n)
+    return build_core(d, s, kb, ko, vb, vo, n, st, root, n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap,
+                      digests, host_out);
+  if (kept == 0) return nothing_left(s, root, n_nodes, n_bytes, node_off, host_out);
+  std::vector<uint8_t> hk(hko[n] - hko[0]), hv(hvo[n] - hvo[0]);
+  if (!hk.empty()) HIP_OK(hipMemcpyAsync(hk.data(), kb + hko[0], hk.size(), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(hv.data(), vb + hvo[0], hv.size(), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  std::vector<uint64_t> cko(kept + 1, 0), cvo(kept + 1, 0);
+  std::vector<uint8_t> ck, cv;
+  uint64_t k = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (hvo[i + 1] == hvo[i]) continue;
+    ck.insert(ck.end(), hk.begin() + (hko[i] - hko[0]), hk.begin() + (hko[i + 1] - hko[0]));
+    cv.insert(cv.end(), hv.begin() + (hvo[i] - hvo[0]), hv.begin() + (hvo[i + 1] - hvo[0]));
+    ++k;
+    cko[k] = ck.size();
+    cvo[k] = cv.size();
+  }
+  ck.resize(ck.size() + 16, 0);
+  cv.resize(cv.size() + 16, 0);
+  TmpBuf<uint8_t> dkb, dvb;
+  TmpBuf<uint64_t> dko, dvo;
+  StreamDrain tail{s};
+  HIP_OK(dkb.put(ck.data(), ck.size(), s));
+  HIP_OK(dvb.put(cv.data(), cv.size(), s));
+  HIP_OK(dko.put(cko.data(), kept + 1, s));
+  HIP_OK(dvo.put(cvo.data(), kept + 1, s));
+  return build_core(d, s, dkb.p, dko.p, dvb.p, dvo.p, kept, st, root, n_nodes, n_bytes, node_blob, blob_cap, node_off,
+                    node_cap, digests, host_out);
+}
+
 // The update over device keys and values (sorted, distinct): the merge of
 // pv_trie_update.h, then build_core over the merged items.  old_root, root,
 // n_nodes and n_bytes are host memory; the node outputs as build_core's.
+// removals (pv_state_apply): an empty value removes its key.
 int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_root, const uint8_t* kb,
                 const uint64_t* ko, const uint8_t* vb, const uint64_t* vo, uint64_t n, bool insert, uint8_t* root,
                 uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
-                uint64_t node_cap, uint8_t* digests, bool host_out) {
-  if (memcmp(old_root, kBlankRoot, 32) == 0)   // nothing to merge with: the store is not read
+                uint64_t node_cap, uint8_t* digests, bool host_out, bool removals = false) {
+  const bool blank = memcmp(old_root, kBlankRoot, 32) == 0;
+  if (blank && !removals)   // nothing to merge with: the store is not read
     return build_core(d, s, kb, ko, vb, vo, n, insert ? &st : nullptr, root, n_nodes, n_bytes, node_blob, blob_cap,
                       node_off, node_cap, digests, host_out);
+  const char* const what = removals ? "state apply" : "state update";
   if (n_nodes) *n_nodes = 0;
   if (n_bytes) *n_bytes = 0;
   const int mb = merkle_blocks(d);
@@ -3479,12 +3542,18 @@ int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_roo
   b.n = n;
   HIP_OK(h.alloc(n + 1));
   b.tree = h.p;
-  uint32_t hs[4] = {0, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-  HIP_OK(stats.put(hs, 4, s));
+  uint32_t hs[5] = {0, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0};   // hs[4]: the batch holds a removal
+  HIP_OK(stats.put(hs, 5, s));
+  if (removals) b.empty_seen = stats.p + 4;
   HIP_OK(pv::launch_trie_build_lcp(b, stats.p, mb, s));
-  HIP_OK(hipMemcpyAsync(hs, stats.p, 16, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(hs, stats.p, 20, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   if (const int rc = lcp_refusal(hs)) return rc;
+  // a batch without a removal is a batch of sets: it takes the walk without the removal mode
+  const bool opening = removals && hs[4] != 0;
+  if (blank)
+    return build_without_removals(d, s, kb, ko, vb, vo, n, insert ? &st : nullptr, root, n_nodes, n_bytes, node_blob,
+                                  blob_cap, node_off, node_cap, digests, host_out);
   // count, scan, write
   pv::TuCtx c{};
   c.blob = st.blob;
@@ -3511,7 +3580,7 @@ int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_roo
   c.vbytes = sizes.p + 2 * (n + 1);
   HIP_OK(status.alloc(n));
   c.status = status.p;
-  HIP_OK(pv::launch_trie_update_count(c, mb, s));
+  HIP_OK(opening ? pv::launch_trie_apply_count(c, mb, s) : pv::launch_trie_update_count(c, mb, s));
   std::vector<uint8_t> hstat(n);
   HIP_OK(hipMemcpyAsync(hstat.data(), status.p, n, hipMemcpyDeviceToHost, s));
   HIP_OK(d.scan.ensure(pv::scan_sums_words(n + 1)));
@@ -3526,12 +3595,16 @@ int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_roo
     if (hstat[j] != pv::SP_OK)
       return fail(PV_EINVAL,
                   hstat[j] == pv::SP_NODE_MISSING
-                      ? "state update: key %llu: the root or a node on its path is not in the store (status %u)"
-                      : "state update: key %llu: a node on its path is not a well-formed trie node (status %u)",
-                  (unsigned long long)j, (unsigned)hstat[j]);
-  if (tot[0] < n || tot[0] > pv::TB_MAX_KEYS)
-    return fail(PV_EINVAL, "state update: %llu merged items, above the 2^28 of one build", (unsigned long long)tot[0]);
+                      ? "%s: key %llu: the root or a node on its path is not in the store (status %u)"
+                      : "%s: key %llu: a node on its path is not a well-formed trie node (status %u)",
+                  what, (unsigned long long)j, (unsigned)hstat[j]);
+  if ((!removals && tot[0] < n) || tot[0] > pv::TB_MAX_KEYS)
+    return fail(PV_EINVAL, "%s: %llu merged items, above the 2^28 of one build", what, (unsigned long long)tot[0]);
   const uint64_t items = tot[0];
+  if (items == 0) {   // every key of the state removed: no build launch
+    tail.done = true;
+    return nothing_left(s, root, n_nodes, n_bytes, node_off, host_out);
+  }
   HIP_OK(ikey.alloc(tot[1] + 16));
   HIP_OK(ival.alloc(tot[2] + 16));
   HIP_OK(ikoff.alloc(items + 1));
@@ -3548,7 +3621,7 @@ int update_core(Device& d, hipStream_t s, StateStore& st, const uint8_t* old_roo
   c.ivoff = ivoff.p;
   c.inib = inib.p;
   c.ikind = ikind.p;
-  HIP_OK(pv::launch_trie_update_emit(c, mb, s));
+  HIP_OK(opening ? pv::launch_trie_apply_emit(c, mb, s) : pv::launch_trie_update_emit(c, mb, s));
   return build_core(d, s, ikey.p, ikoff.p, ival.p, ivoff.p, items, insert ? &st : nullptr, root, n_nodes, n_bytes,
                     node_blob, blob_cap, node_off, node_cap, digests, host_out, inib.p, ikind.p);
 }
@@ -3561,17 +3634,11 @@ int update_empty(Entry& en, void* stream, const uint8_t* old_root, uint8_t* new_
   return build_empty(en, stream, nullptr, n_nodes, n_bytes, node_off, host_out);
 }
 
-}  // namespace
-
-extern "C" {
-
-// A 3PC batch of PruningState.set onto the state at a committed root, and the new headHash
-// (state/pruning_state.py:60-61, 136; Trie.update, state/trie/pruning_trie.py:1006-1027), as one
-// batch over device buffers; see include/plenum_verify.h.
-int pv_state_update_device(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
-                           const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert,
-                           uint8_t* new_root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
-                           uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, void* stream) {
+// pv_state_update_device / pv_state_apply_device: device buffers, strictly increasing keys
+int update_device_entry(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                        const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                        uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                        uint64_t node_cap, uint8_t* digests, void* stream, bool removals) {
   Entry en;
   if (n == 0) {   // as the empty build: nothing is looked at, the store included
     if (const int rc = en.check()) return rc;
@@ -3587,15 +3654,14 @@ int pv_state_update_device(int32_t store, const uint8_t* old_root, const uint8_t
   if (digests && misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
   if (const int rc = en.begin(stream)) return rc;
   return update_core(*en.d, en.s, *st, old_root, key_blob, key_off, val_blob, val_off, n, insert != 0, new_root,
-                     n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap, digests, false);
+                     n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap, digests, false, removals);
 }
 
-// The host form of the same (state/pruning_state.py:60-61; state/trie/pruning_trie.py:1006-1027):
-// keys in any order, the last of equal keys wins, as a sequence of sets gives.
-int pv_state_update(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
-                    const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
-                    uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
-                    uint64_t node_cap, uint8_t* digests) {
+// pv_state_update / pv_state_apply: host buffers, keys in any order, the last of equal keys wins
+int update_host_entry(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                      const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                      uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                      uint64_t node_cap, uint8_t* digests, bool removals) {
   if (n == 0) {
     Entry en;
     if (const int rc = en.check()) return rc;
@@ -3605,7 +3671,7 @@ int pv_state_update(int32_t store, const uint8_t* old_root, const uint8_t* key_b
   if (!old_root || !new_root) return fail(PV_EINVAL, "null pointer");
   std::vector<uint64_t> ko, vo;
   std::vector<uint8_t> kb, vb;
-  if (const int rc = sorted_pairs(key_blob, key_off, val_blob, val_off, n, ko, vo, kb, vb)) return rc;
+  if (const int rc = sorted_pairs(key_blob, key_off, val_blob, val_off, n, ko, vo, kb, vb, removals)) return rc;
   const uint64_t m = ko.size() - 1;
   Entry en;
   StateStore* st;
@@ -3620,7 +3686,55 @@ int pv_state_update(int32_t store, const uint8_t* old_root, const uint8_t* key_b
   HIP_OK(dko.put(ko.data(), m + 1, s));
   HIP_OK(dvo.put(vo.data(), m + 1, s));
   return update_core(*en.d, s, *st, old_root, dkb.p, dko.p, dvb.p, dvo.p, m, insert != 0, new_root, n_nodes, n_bytes,
-                     node_blob, blob_cap, node_off, node_cap, digests, true);
+                     node_blob, blob_cap, node_off, node_cap, digests, true, removals);
+}
+
+}  // namespace
+
+extern "C" {
+
+// A 3PC batch of PruningState.set onto the state at a committed root, and the new headHash
+// (state/pruning_state.py:60-61, 136; Trie.update, state/trie/pruning_trie.py:1006-1027), as one
+// batch over device buffers; see include/plenum_verify.h.
+int pv_state_update_device(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                           const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert,
+                           uint8_t* new_root, uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob,
+                           uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap, uint8_t* digests, void* stream) {
+  return update_device_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
+                             n_bytes, node_blob, blob_cap, node_off, node_cap, digests, stream, false);
+}
+
+// The host form of the same (state/pruning_state.py:60-61; state/trie/pruning_trie.py:1006-1027):
+// keys in any order, the last of equal keys wins, as a sequence of sets gives.
+int pv_state_update(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                    const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                    uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                    uint64_t node_cap, uint8_t* digests) {
+  return update_host_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
+                           n_bytes, node_blob, blob_cap, node_off, node_cap, digests, false);
+}
+
+// A 3PC batch of PruningState.set and PruningState.remove onto the state at a committed root, and
+// the new headHash (state/pruning_state.py:60-61, 84-85, 136; Trie.update and Trie.delete,
+// state/trie/pruning_trie.py:1006-1027, 683-848), as one batch over device buffers: an empty
+// value removes its key; see include/plenum_verify.h.
+int pv_state_apply_device(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                          const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                          uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap,
+                          uint64_t* node_off, uint64_t node_cap, uint8_t* digests, void* stream) {
+  return update_device_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
+                             n_bytes, node_blob, blob_cap, node_off, node_cap, digests, stream, true);
+}
+
+// The host form of the same (state/pruning_state.py:60-61, 84-85; state/trie/pruning_trie.py:683-848,
+// 1006-1027): keys in any order, the last of equal keys wins, a removal over a set as a set over a
+// removal, as the sequence of calls gives.
+int pv_state_apply(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
+                   const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
+                   uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
+                   uint64_t node_cap, uint8_t* digests) {
+  return update_host_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
+                           n_bytes, node_blob, blob_cap, node_off, node_cap, digests, true);
 }
 
 }  // extern "C"

@@ -249,6 +249,11 @@ struct TuCtx;
 hipError_t launch_trie_update_count(const TuCtx& c, int max_blocks, hipStream_t s);
 hipError_t launch_trie_update_emit(const TuCtx& c, int max_blocks, hipStream_t s);
 
+// Sets and removals onto a committed root: the same two passes with tu_walk_t<true>, in which the
+// lane of an empty value is a removal (it emits no value and opens the children it carries).
+hipError_t launch_trie_apply_count(const TuCtx& c, int max_blocks, hipStream_t s);
+hipError_t launch_trie_apply_emit(const TuCtx& c, int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

@@ -2031,6 +2031,33 @@ hipError_t launch_trie_update_emit(const TuCtx& c, int max_blocks, hipStream_t s
   return hipGetLastError();
 }
 
+// ------------------------------------------------- sets and removals onto a committed root
+// The same launch shape over tu_walk_t<true>: the lane of an empty value removes its key and
+// opens the child references it carries (pv_trie_update.h).  Kernels of their own, so that
+// the update kernels above stay the instantiation without removals.
+__global__ __launch_bounds__(256) void k_trie_apply_count(TuCtx c) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < c.n; j += stride)
+    c.status[j] = (uint8_t)tu_walk_t<true>(c, j, false);
+}
+
+__global__ __launch_bounds__(256) void k_trie_apply_emit(TuCtx c) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < c.n; j += stride) (void)tu_walk_t<true>(c, j, true);
+}
+
+hipError_t launch_trie_apply_count(const TuCtx& c, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_apply_count, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_apply_emit(const TuCtx& c, int max_blocks, hipStream_t s) {
+  if (c.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_apply_emit, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------- synthetic workload
 // Deterministic generator, spec in plenum_gpu/synth.py.
 // Three layouts: FIXED (C2: every M mlen bytes), RANGE (C4: len uniform in

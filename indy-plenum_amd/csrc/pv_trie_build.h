@@ -100,6 +100,9 @@ struct TbCtx {
   // A merged item list (pv_trie_update.h) instead of plain keys; both null for a plain build.
   const uint32_t* knib;    // n: the nibble length of path i (an odd path ends in a zero pad nibble); null: 2 per byte
   const uint8_t* kind;     // n: 1 = the value of item i is a child reference carried as it is (TU_SUBTREE); null: none
+  // The batch check of pv_state_apply alone.  Non-null: tb_lcp_one admits an empty value (a removal) and
+  // sets *empty_seen to 1 when it meets one (every writer stores the same word).  Null for every build.
+  uint32_t* empty_seen;
 };
 
 // number of tree levels over n keys and their offsets (lvoff[0 .. nlv]); the words of the whole tree
@@ -132,6 +135,7 @@ PV_HD uint32_t tb_lcp_one(const TbCtx& c, uint64_t i, uint32_t& bad) {
   if (i < c.n) {
     const uint64_t a = c.val_off[i], b = c.val_off[i + 1];
     if (b < a) bad |= TB_BAD_OFFSET;
+    else if (b == a && c.empty_seen) *c.empty_seen = 1;
     else if (b == a || b - a > TB_MAX_VAL_BYTES || (tb_subtree(c, i) && b - a > 33)) bad |= TB_BAD_VALUE;
     const uint64_t ka = c.key_off[i], kb = c.key_off[i + 1];
     if (kb < ka || kb - ka > TB_MAX_KEY_BYTES) bad |= TB_BAD_OFFSET;

@@ -45,6 +45,25 @@
 // time.  A missing or malformed node gives the key a PV_SP_* status and the
 // caller refuses the whole call.
 //
+// Removals (tu_walk_t<true>, behind pv_state_apply).  A batch item with an empty
+// value removes its key: PruningState.remove (state/pruning_state.py:84-85 ->
+// Trie.delete, state/trie/pruning_trie.py:683-848), the one trie operation that
+// restructures upward.  The lane of a removed key walks and carries as above,
+// emits no VALUE(K_j), and OPENS every child reference it carries from a branch
+// slot at path Q (tu_open: a hashed reference through ts_find, an inline node in
+// place).  A branch: the item stays SUBTREE at Q.  A leaf with path P: VALUE at
+// Q + P with the leaf's value.  An extension with path P: SUBTREE at Q + P with
+// the extension's child reference.  The builder turns a SUBTREE with nibbles left
+// below its slot into an extension over its payload, which is canonical only over
+// a branch; nibbles are left only where the old branch above the child collapsed,
+// and a branch collapses only if every batch key that visits it is a removal (a
+// set leaves a VALUE there), so every child that can end up alone was carried by
+// a removal lane and is in its canonical item form.  Where nothing collapses the
+// opened item re-encodes to the bytes it had.  The child of an extension is
+// carried unopened: in a trie the reference wrote it is a branch.  Lanes of set
+// keys carry references unopened.  Count mode opens too (path and payload sizes
+// depend on it), and so does the sizing pass of an AFTER group.
+//
 // The host twin is tu_walk called in index order.
 #pragma once
 #include <stdint.h>
@@ -62,7 +81,8 @@ struct TuCtx {
   const uint32_t *dig, *table;
   uint32_t slots, n_nodes;
   const uint32_t* root;   // 8 words, not the blank root
-  // the batch: sorted distinct keys, non-empty values (checked by tb_lcp_one before)
+  // the batch: sorted distinct keys, values (checked by tb_lcp_one before) non-empty, or empty for a removal
+  // where the walk takes removals
   const uint8_t* key_blob;
   const uint64_t* key_off;
   const uint8_t* val_blob;
@@ -120,12 +140,12 @@ PV_HD uint32_t tu_cmp(const uint8_t* p, uint64_t skip, uint64_t pn, const uint8_
   return a < b ? 3u : 4u;
 }
 
-// One item at `at`: the path is key[:D] followed by the nibble `slot` (< 16) or
-// by pn path nibbles of p; the payload is src[0 .. len).  Count mode (!write)
-// only advances `at`.
+// One item at `at`: the path is key[:D], then the nibble `slot` if it is < 16,
+// then pn path nibbles of p (hex-prefix bytes, from nibble `skip`); the payload
+// is src[0 .. len).  Count mode (!write) only advances `at`.
 PV_HD void tu_put(const TuCtx& c, bool write, TuCur& at, const uint8_t* key, uint64_t D, const uint8_t* p,
                   uint64_t skip, uint64_t pn, uint32_t slot, uint8_t kind, const uint8_t* src, uint64_t len) {
-  const uint64_t nib = D + (slot < 16 ? 1 : pn), nb = (nib + 1) / 2;
+  const uint64_t P = D + (slot < 16 ? 1 : 0), nib = P + pn, nb = (nib + 1) / 2;
   if (write) {
     uint8_t* w = c.ikey + at.k;
     for (uint64_t b = 0; b < nb; ++b) {
@@ -134,7 +154,8 @@ PV_HD void tu_put(const TuCtx& c, bool write, TuCur& at, const uint8_t* key, uin
         const uint64_t x = 2 * b + half;
         uint32_t q = 0;   // the pad nibble of an odd path
         if (x < D) q = sp_nibble(key, x);
-        else if (x < nib) q = slot < 16 ? slot : sp_nibble(p, skip + (x - D));
+        else if (x < P) q = slot;
+        else if (x < nib) q = sp_nibble(p, skip + (x - P));
         v = 16 * v + q;
       }
       w[b] = (uint8_t)v;
@@ -151,9 +172,93 @@ PV_HD void tu_put(const TuCtx& c, bool write, TuCur& at, const uint8_t* key, uin
   at.v += len;
 }
 
+// The item a child reference stands for once its node is opened.
+struct TuOpen {
+  uint8_t kind;
+  const uint8_t* p;   // the opened node's hex-prefix path: pn nibbles from nibble `skip` (a branch: none)
+  uint64_t skip, pn;
+  const uint8_t* src;
+  uint64_t len;
+};
+
+// Open the reference blob[pos .. pos + rlen) (from tu_ref: rlen != 0).  A branch:
+// the reference as it is.  A leaf: its path and value.  An extension: its path
+// and its child reference.  SP_NODE_MISSING: the node is not in the store;
+// SP_MALFORMED: it is no trie node.
+PV_HD uint32_t tu_open(const TuCtx& c, uint64_t pos, uint64_t rlen, bool hashed, TuOpen& o) {
+  const uint8_t* blob = c.blob;
+  o = TuOpen{TU_SUBTREE, blob, 0, 0, blob + pos, rlen};
+  uint64_t cb = pos, ce = pos + rlen;
+  if (hashed) {
+    uint32_t t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const uint8_t* q = blob + pos + 1 + 4 * k;
+      t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    }
+    const uint32_t id = ts_find(c.table, c.slots, c.dig, c.n_nodes, t);
+    if (id == TS_ABSENT) return SP_NODE_MISSING;
+    cb = c.beg[id];
+    ce = c.end[id];
+  }
+  bool is_list;
+  uint64_t pb, pe;
+  if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) return SP_MALFORMED;
+  uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0;
+  bool i0l = false, i1l = false;
+  uint32_t count = 0;
+  uint64_t at = pb;
+  while (at < pe) {
+    bool il;
+    uint64_t ib, ie;
+    if (count == 17 || !rlp_item(blob, at, pe, il, ib, ie)) return SP_MALFORMED;
+    if (count == 0) i0b = ib, i0e = ie, i0l = il;
+    if (count == 1) i1s = at, i1b = ib, i1e = ie, i1l = il;
+    at = ie;
+    ++count;
+  }
+  if (count == 17) return SP_OK;
+  if (count != 2 || i0l || i0e == i0b) return SP_MALFORMED;
+  const uint8_t* p = blob + i0b;
+  const uint32_t flags = p[0] >> 4, odd = flags & 1u;
+  const uint64_t pn = 2 * (i0e - i0b - 1) + odd, skip = 2 - odd;
+  if (flags & 2u) {
+    if (i1l || i1e == i1b) return SP_MALFORMED;
+    o = TuOpen{TU_VALUE, p, skip, pn, blob + i1b, i1e - i1b};
+    return SP_OK;
+  }
+  if (pn == 0) return SP_MALFORMED;
+  uint64_t len;
+  bool h2;
+  const uint32_t r = tu_ref(i1s, i1l, i1b, i1e, len, h2);
+  if (r != SP_OK) return r;
+  if (len == 0) return SP_MALFORMED;
+  o = TuOpen{TU_SUBTREE, p, skip, pn, blob + i1s, len};
+  return SP_OK;
+}
+
+// The child reference blob[pos .. pos + rlen) of slot t of the branch at depth D,
+// carried as an item: as it is, or, by the lane of a removed key, opened.
+PV_HD uint32_t tu_carry(const TuCtx& c, bool open, bool write, TuCur& at, const uint8_t* key, uint64_t D, uint32_t t,
+                        uint64_t pos, uint64_t rlen, bool hashed) {
+  if (!open) {
+    tu_put(c, write, at, key, D, key, 0, 0, t, TU_SUBTREE, c.blob + pos, rlen);
+    return SP_OK;
+  }
+  TuOpen o;
+  const uint32_t r = tu_open(c, pos, rlen, hashed, o);
+  if (r != SP_OK) return r;
+  tu_put(c, write, at, key, D, o.p, o.skip, o.pn, t, o.kind, o.src, o.len);
+  return SP_OK;
+}
+
 // The walk of batch key j.  Count mode: cnt / pbytes / vbytes [j] and status[j].
 // Write mode (after the scans, every status SP_OK): the items of key j.
-PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) {
+// REMOVALS: an empty value removes key j (see the head of this file); without
+// it no value is empty and the walk is the one of a batch of sets.
+template <bool REMOVALS>
+PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
+  const bool rem = REMOVALS && c.val_off[j + 1] == c.val_off[j];
   const uint8_t* key = c.key_blob + c.key_off[j];
   const uint64_t knib = 2 * (c.key_off[j + 1] - c.key_off[j]);
   const uint32_t hl = c.h[j], hr = c.h[j + 1];
@@ -232,11 +337,16 @@ PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) {
               break;
             }
             if (rlen) {
+              uint32_t ro = SP_OK;
               if (pass == 0) {
-                if (after) tu_put(c, false, grp, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
-                else if (!write) tu_put(c, false, front, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
+                if (after) ro = tu_carry(c, rem, false, grp, key, D, (uint32_t)t, pos, rlen, hashed);
+                else if (!write) ro = tu_carry(c, rem, false, front, key, D, (uint32_t)t, pos, rlen, hashed);
               } else {
-                tu_put(c, true, before ? front : w, key, D, key, 0, 0, (uint32_t)t, TU_SUBTREE, blob + pos, rlen);
+                ro = tu_carry(c, rem, true, before ? front : w, key, D, (uint32_t)t, pos, rlen, hashed);
+              }
+              if (ro != SP_OK) {
+                bad = ro;
+                break;
               }
             }
           }
@@ -336,7 +446,8 @@ PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) {
     ce = c.end[id];
   }
   if (st != SP_OK) return st;
-  tu_put(c, write, front, key, knib, key, 0, 0, 16, TU_VALUE, c.val_blob + c.val_off[j], c.val_off[j + 1] - c.val_off[j]);
+  if (!rem)
+    tu_put(c, write, front, key, knib, key, 0, 0, 16, TU_VALUE, c.val_blob + c.val_off[j], c.val_off[j + 1] - c.val_off[j]);
   if (!write) {
     c.cnt[j] = front.i;
     c.pbytes[j] = front.k;
@@ -344,5 +455,8 @@ PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) {
   }
   return SP_OK;
 }
+
+// a batch of sets (pv_state_update): no value is empty
+PV_HD uint32_t tu_walk(const TuCtx& c, uint64_t j, bool write) { return tu_walk_t<false>(c, j, write); }
 
 }  // namespace pv

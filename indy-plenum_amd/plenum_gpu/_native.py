@@ -123,6 +123,15 @@ SIGNATURES = [
      [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
       ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
       ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp]),
+    # as pv_state_update[_device]; an empty value removes its key
+    ('pv_state_apply', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
+      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp]),
+    ('pv_state_apply_device', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
+      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_state_store_prove', ctypes.c_int,
      [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
       _vp, ctypes.c_uint64]),

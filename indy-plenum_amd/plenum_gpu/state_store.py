@@ -43,8 +43,17 @@ reference would return [b''].
   the store and carries the children no batch key enters as they are, and the build runs over the
   merged list; `update_host(db, root, items)` is its pure-Python mirror over a {hash: RLP} dict.
 
-Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal),
-deletion and pruning of nodes.
+* `GpuStateStore.apply_batch(root, items)` / `remove_keys(root, keys)` -- pv_state_apply: a batch
+  of sets and removals (a value of None: PruningState.remove, state/pruning_state.py:84-85 ->
+  Trie.delete, state/trie/pruning_trie.py:683-848) in one call.  The lane of a removed key emits no
+  value and opens the children it carries from the branches on its path (a leaf child as its path and
+  value, an extension child as its path and child reference), so a branch left with one entry
+  collapses in the build; `apply_host(db, root, items)` is the pure-Python mirror.  A removal needs
+  the nodes referenced from the branches on its path in the store, where the reference decodes a
+  sibling only on a collapse.  `update_state` and `build_state` keep refusing an empty value.
+
+Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal) and
+pruning of nodes no root reaches.
 """
 import ctypes
 import hashlib
@@ -330,9 +339,48 @@ def _lcp(a, b):
     return m
 
 
+def _open_ref(db, blob, it, ref):
+    """tu_open of csrc/pv_trie_update.h: the non-blank child reference `ref` (item `it` of the node
+    in `blob`) -> (status, path nibbles, kind, payload) of the item it stands for once its node is
+    opened.  A branch: no nibbles and the reference as it is.  A leaf: its path and value.  An
+    extension: its path and its child reference."""
+    if it[1]:                                           # an inline node, read in place
+        node, cb, ce = blob, it[0], it[3]
+    else:
+        node = db.get(ref[1:])
+        if node is None:
+            return PV_SP_NODE_MISSING, [], 0, b''
+        cb, ce = 0, len(node)
+    f = _node_fields(node, cb, ce)
+    if f is None:
+        return PV_SP_MALFORMED, [], 0, b''
+    if len(f) == 17:
+        return PV_SP_OK, [], ITEM_SUBTREE, ref
+    _, pl, pb, pe = f[0]
+    if pl or pe == pb:
+        return PV_SP_MALFORMED, [], 0, b''
+    flags = node[pb] >> 4
+    odd = flags & 1
+    path = [_nibble(node, pb, 2 - odd + i) for i in range(2 * (pe - pb - 1) + odd)]
+    if flags & 2:
+        _, vl, vb, ve = f[1]
+        if vl or ve == vb:
+            return PV_SP_MALFORMED, [], 0, b''
+        return PV_SP_OK, path, ITEM_VALUE, bytes(node[vb:ve])
+    if not path:
+        return PV_SP_MALFORMED, [], 0, b''
+    st, child = _child_ref(node, f[1])
+    if st != PV_SP_OK or not child:
+        return st or PV_SP_MALFORMED, [], 0, b''
+    return PV_SP_OK, path, ITEM_SUBTREE, child
+
+
 def _merge_key(db, root, keys, j, value):
     """The walk of batch key j (tu_walk of csrc/pv_trie_update.h) -> (status, its items in order):
-    the old trie's values and subtrees it carries before itself, its own VALUE, those after."""
+    the old trie's values and subtrees it carries before itself, its own VALUE, those after.
+    An empty `value` removes the key (apply_encoded_host only): no VALUE of its own, and every
+    child reference carried from a branch slot is opened (_open_ref)."""
+    remove = not value
     k = keys[j]
     kp = keys[j - 1] if j else None
     lp = _lcp(kp, k) if j else -1
@@ -361,7 +409,13 @@ def _merge_key(db, root, keys, j, value):
                 if st != PV_SP_OK:
                     return st, []
                 if ref:
-                    (before if t < s else group).append((k[:depth] + [t], ITEM_SUBTREE, ref))
+                    item = (k[:depth] + [t], ITEM_SUBTREE, ref)
+                    if remove:
+                        st, path, kind, payload = _open_ref(db, blob, f[t], ref)
+                        if st != PV_SP_OK:
+                            return st, []
+                        item = (item[0] + path, kind, payload)
+                    (before if t < s else group).append(item)
             if group:
                 after.append(group)
             if s < 0:
@@ -418,7 +472,8 @@ def _merge_key(db, root, keys, j, value):
             cb, ce = 0, len(blob)
     else:
         return PV_SP_MALFORMED, []                      # the step bound ran out
-    return PV_SP_OK, before + [(k, ITEM_VALUE, value)] + [it for g in reversed(after) for it in g]
+    own = [] if remove else [(k, ITEM_VALUE, value)]
+    return PV_SP_OK, before + own + [it for g in reversed(after) for it in g]
 
 
 def merge_host(db, root, pairs):
@@ -514,6 +569,51 @@ def update_host(db, root, items):
     return update_encoded_host(db, root, _pairs(items))
 
 
+# ------------------------------------------------------------------ sets and removals
+def _ops(items):
+    """(key, raw value or None) pairs -> sorted [(key, rlp([value]) or b'' for a removal)], the last
+    of equal keys kept: a later removal beats an earlier set and the other way round"""
+    last = {}
+    for key, value in items:
+        key = key.encode() if isinstance(key, str) else bytes(key)
+        if value is None:
+            last[key] = b''
+            continue
+        value = value.encode() if isinstance(value, str) else bytes(value)
+        if not value:
+            raise ValueError('an empty value is no value; None removes a key')
+        last[key] = rlp_encode([value])
+    return sorted(last.items())
+
+
+def apply_encoded_host(db, root, pairs):
+    """pv_state_apply in Python: sorted distinct (key, encoded value) pairs, an empty encoded value
+    a removal, applied to the trie at `root` whose nodes are in `db` -> (new root, {hash: node RLP}
+    of the emitted nodes).  The merge of update_encoded_host with one rule added: the walk of a
+    removed key emits no value and opens the children it carries (_merge_key).  KeyError when the
+    root, a node on a key's path or a child referenced from a branch on a removed key's path is not
+    in db, ValueError for a malformed one."""
+    root = bytes(root)
+    if not pairs:
+        return root, {}
+    if root == BLANK_ROOT:                              # removals of nothing are dropped
+        return build_encoded_host([p for p in pairs if p[1]])
+    st, j, items = merge_host(db, root, pairs)
+    if st == PV_SP_NODE_MISSING:
+        raise KeyError('key {}: the root or a node on its path is not in the store'.format(j))
+    if st != PV_SP_OK:
+        raise ValueError('key {}: a node on its path is not a well-formed trie node'.format(j))
+    if not items:
+        return BLANK_ROOT, {}
+    return build_items_host(items)
+
+
+def apply_host(db, root, items):
+    """(key, raw value or None) pairs in any order, the last of equal keys wins, applied to the trie
+    at `root` as PruningState.set and PruningState.remove (None) do -> (new root, emitted nodes)"""
+    return apply_encoded_host(db, root, _ops(items))
+
+
 def _root_ptr(root):
     return root.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
@@ -544,11 +644,13 @@ def _build_gpu(pairs, store_id, want_nodes=False):
     return root.tobytes(), nn.value, nb.value, blob[:nb.value], off, dig[:nn.value]
 
 
-def _update_gpu(store_id, root, pairs, insert=True, want_nodes=False):
-    """pv_state_update over (key, encoded value) pairs -> (new root, n_nodes, n_bytes[, blob, off, digests]).
+def _update_gpu(store_id, root, pairs, insert=True, want_nodes=False, entry='pv_state_update'):
+    """pv_state_update (or, with entry, pv_state_apply: an empty encoded value removes its key) over (key,
+    encoded value) pairs -> (new root, n_nodes, n_bytes[, blob, off, digests]).
     With want_nodes the sizing call computes only and the retry inserts, so nothing is inserted twice."""
     nat.ensure_init()
     lib = nat.load()
+    fn = getattr(lib, entry)
     n = len(pairs)
     kblob, koff = nat.pack_messages([k for k, _ in pairs])
     vblob, voff = nat.pack_messages([v for _, v in pairs])
@@ -557,18 +659,22 @@ def _update_gpu(store_id, root, pairs, insert=True, want_nodes=False):
     nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
 
     def call(ins, blob, bcap, off, ncap, dig):
-        return lib.pv_state_update(store_id, _root_ptr(old), _p(kblob), _p(koff), _p(vblob), _p(voff), n, int(ins),
-                                   _root_ptr(new), ctypes.byref(nn), ctypes.byref(nb), _p(blob), bcap, _p(off), ncap,
-                                   _p(dig))
+        return fn(store_id, _root_ptr(old), _p(kblob), _p(koff), _p(vblob), _p(voff), n, int(ins), _root_ptr(new),
+                  ctypes.byref(nn), ctypes.byref(nb), _p(blob), bcap, _p(off), ncap, _p(dig))
     if not want_nodes:
-        nat._check('pv_state_update', call(insert, None, 0, None, 0, None))
+        nat._check(entry, call(insert, None, 0, None, 0, None))
         return new.tobytes(), nn.value, nb.value
-    nat._check('pv_state_update', call(False, None, 0, None, 0, None))   # sizes
+    nat._check(entry, call(False, None, 0, None, 0, None))   # sizes
     blob = np.zeros(max(nb.value, 1), np.uint8)
     off = np.zeros(nn.value + 1, np.uint64)
     dig = np.zeros((max(nn.value, 1), 32), np.uint8)
-    nat._check('pv_state_update', call(insert, blob, nb.value, off, nn.value, dig))
+    nat._check(entry, call(insert, blob, nb.value, off, nn.value, dig))
     return new.tobytes(), nn.value, nb.value, blob[:nb.value], off, dig[:nn.value]
+
+
+def _apply_gpu(store_id, root, pairs, insert=True, want_nodes=False):
+    """pv_state_apply over (key, encoded value) pairs, an empty encoded value a removal"""
+    return _update_gpu(store_id, root, pairs, insert, want_nodes, entry='pv_state_apply')
 
 
 def state_root_batch(items):
@@ -672,6 +778,27 @@ class GpuStateStore:
             if 'state update: key ' in text:
                 raise (KeyError if 'is not in the store' in text else ValueError)(text) from None
             raise
+
+    def apply_batch(self, root, items):
+        """Apply (key, raw value or None) pairs to the state at the committed `root` on the device
+        (pv_state_apply) and insert the nodes it emits -> the new root hash: one 3PC batch of
+        PruningState.set and, for a value of None, PruningState.remove (state/pruning_state.py:60-61,
+        84-85), the last of equal keys winning.  Removing a key the state does not hold changes
+        nothing; removing every key gives BLANK_ROOT.  `root` and every earlier root stay provable.
+        KeyError when the root, a node on a key's path or a node referenced from a branch on a
+        removed key's path is not in the store, ValueError for a node that is no trie node."""
+        try:
+            return _apply_gpu(self._id, root_hash_of(root), _ops(items))[0]
+        except nat.PlenumGpuError as exc:
+            text = str(exc)
+            if 'state apply: key ' in text:
+                raise (KeyError if 'is not in the store' in text else ValueError)(text) from None
+            raise
+
+    def remove_keys(self, root, keys):
+        """PruningState.remove of every key (state/pruning_state.py:84-85) at the committed `root`
+        -> the new root hash"""
+        return self.apply_batch(root, [(k, None) for k in keys])
 
     def add_serialized_proof(self, data):
         """Add the nodes of a serialized proof (rlp(list of nodes)) -> the number new to the store"""

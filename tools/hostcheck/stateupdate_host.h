@@ -4,7 +4,10 @@
 // over the batch (its checks and h[]), tu_walk per key in count mode, the three
 // exclusive scans, tu_walk per key in write mode, then the build of
 // statebuild_host.h over the merged items.  Every work array has its exact
-// size.  Shared by libstateupdatecheck.so and stateupdatecheck_asan.
+// size.  Shared by libstateupdatecheck.so and stateupdatecheck_asan, and, with
+// `removals` (what pv_state_apply_device runs: tb_lcp_one admits an empty value
+// and the walk is tu_walk_t<true> if the batch holds one), by libstateapplycheck.so and
+// stateapplycheck_asan.
 #pragma once
 #include "statebuild_host.h"
 #include "statestore_host.h"
@@ -25,9 +28,11 @@ struct Merged {
 // the merge alone: the batch (sorted, distinct; checked here as the device form checks it)
 // against the trie at old_root (not the blank root) in the store
 inline int merge(const ssh::View& v, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
-                 const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, Merged& m) {
+                 const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, Merged& m, bool removals = false) {
   m = Merged();
   pv::TbCtx b{};
+  uint32_t empty_seen = 0;
+  if (removals) b.empty_seen = &empty_seen;
   b.key_blob = key_blob;
   b.key_off = key_off;
   b.val_blob = val_blob;
@@ -67,7 +72,9 @@ inline int merge(const ssh::View& v, const uint8_t* old_root, const uint8_t* key
   c.pbytes = pbytes.data();
   c.vbytes = vbytes.data();
   c.status = status.data();
-  for (uint64_t j = 0; j < n; ++j) status[j] = (uint8_t)pv::tu_walk(c, j, false);
+  const bool opening = removals && empty_seen != 0;   // no removal in the batch: the walk of a batch of sets
+  for (uint64_t j = 0; j < n; ++j)
+    status[j] = (uint8_t)(opening ? pv::tu_walk_t<true>(c, j, false) : pv::tu_walk(c, j, false));
   for (uint64_t j = 0; j < n; ++j)
     if (status[j] != pv::SP_OK) return m.bad_index = j, m.status = status[j], BAD_WALK;
   uint64_t tot[3] = {0, 0, 0};
@@ -96,7 +103,7 @@ inline int merge(const ssh::View& v, const uint8_t* old_root, const uint8_t* key
   c.ivoff = m.ivoff.data();
   c.inib = m.inib.data();
   c.ikind = m.ikind.data();
-  for (uint64_t j = 0; j < n; ++j) (void)pv::tu_walk(c, j, true);
+  for (uint64_t j = 0; j < n; ++j) (void)(opening ? pv::tu_walk_t<true>(c, j, true) : pv::tu_walk(c, j, true));
   return OK;
 }
 
@@ -119,7 +126,8 @@ inline void add_hashed(ssh::Store& st, const sbh::Built& b) {
 
 // pv_state_update_device up to the delivery: out.root / n_nodes / n_bytes and the nodes
 inline int update(const ssh::View& v, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
-                  const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, sbh::Built& out, Merged& m) {
+                  const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, sbh::Built& out, Merged& m,
+                  bool removals = false) {
   sbh::Built blank;
   (void)sbh::build(nullptr, nullptr, nullptr, nullptr, 0, blank);
   m = Merged();
@@ -128,14 +136,51 @@ inline int update(const ssh::View& v, const uint8_t* old_root, const uint8_t* ke
     memcpy(out.root, old_root, 32);
     return OK;
   }
-  if (memcmp(old_root, blank.root, 32) == 0) {
+  if (memcmp(old_root, blank.root, 32) == 0 && !removals) {
     const int rc = sbh::build(key_blob, key_off, val_blob, val_off, n, out);
     m.bad_index = out.bad_index;
     return rc;
   }
-  if (const int rc = merge(v, old_root, key_blob, key_off, val_blob, val_off, n, m)) {
+  if (memcmp(old_root, blank.root, 32) == 0) {   // the batch's checks, then the build of the pairs that are no removal
+    pv::TbCtx b{};
+    b.key_blob = key_blob;
+    b.key_off = key_off;
+    b.val_blob = val_blob;
+    b.val_off = val_off;
+    b.n = n;
+    uint32_t empty_seen = 0;
+    b.empty_seen = &empty_seen;
+    uint64_t bad_at[3] = {n + 1, n + 1, n + 1};
+    for (uint64_t i = 0; i <= n; ++i) {
+      uint32_t bad;
+      (void)pv::tb_lcp_one(b, i, bad);
+      for (int k = 0; k < 3; ++k)
+        if ((bad >> k & 1) && i < bad_at[k]) bad_at[k] = i;
+    }
+    out = sbh::Built();
+    if (bad_at[2] <= n) return m.bad_index = bad_at[2], BAD_OFFSET;
+    if (bad_at[1] <= n) return m.bad_index = bad_at[1], BAD_VALUE;
+    if (bad_at[0] <= n) return m.bad_index = bad_at[0], BAD_ORDER;
+    std::vector<uint8_t> kb, vb;
+    std::vector<uint64_t> ko(1, 0), vo(1, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+      if (val_off[i + 1] == val_off[i]) continue;
+      kb.insert(kb.end(), key_blob + key_off[i], key_blob + key_off[i + 1]);
+      vb.insert(vb.end(), val_blob + val_off[i], val_blob + val_off[i + 1]);
+      ko.push_back(kb.size());
+      vo.push_back(vb.size());
+    }
+    const int rc = sbh::build(kb.data(), ko.data(), vb.data(), vo.data(), ko.size() - 1, out);
+    m.bad_index = out.bad_index;
+    return rc;
+  }
+  if (const int rc = merge(v, old_root, key_blob, key_off, val_blob, val_off, n, m, removals)) {
     out = sbh::Built();
     return rc;
+  }
+  if (m.items == 0) {   // every key of the state removed: the blank root, no node
+    out = blank;
+    return OK;
   }
   if (sbh::build(m.ikey.data(), m.ikoff.data(), m.ival.data(), m.ivoff.data(), m.items, out, m.inib.data(),
                  m.ikind.data()) != sbh::OK) {
