@@ -96,10 +96,16 @@ def test_key_status_outside_g2(fx, nat):
     assert e.value.code == -77
 
 
-def test_device_entry_out_of_range_indices(fx, nat):
+# pv_tuning values that select the check kernel for a call of any size
+KERNEL_TUNING = {'pair': {'bls_quad_max': 0, 'bls_oct_max': 0}, 'quad': {'bls_oct_max': 0}, 'oct': {}}
+
+
+@pytest.mark.parametrize('kernel', sorted(KERNEL_TUNING))
+def test_device_entry_out_of_range_indices(fx, nat, kernel):
     """pv_bls_verify_batch_device does not check indices on the host: a check with
     key_idx >= the key count or msg_idx >= n_msgs gets verdict 0 and touches
-    nothing out of range; the in-range checks of the same call are unaffected."""
+    nothing out of range; the in-range checks of the same call are unaffected.
+    Under each of the three check kernels."""
     import torch
     from plenum_gpu.device import _p, _stream
     gb = bytes.fromhex(fx['generator_hex'])
@@ -121,8 +127,12 @@ def test_device_entry_out_of_range_indices(fx, nat):
     midx = torch.tensor(np.array(mid, np.uint32).view(np.int32), device=dev)
     verdict = torch.full((6,), 9, dtype=torch.uint8, device=dev)
     lib = nat.load()
-    nat._bls_check('pv_bls_verify_batch_device', lib.pv_bls_verify_batch_device(
-        _p(sig), _p(blob), _p(off), 2, _p(midx), _p(kidx), 6, _p(verdict), 0, _stream(dev)))
+    prev = nat.set_tuning(**KERNEL_TUNING[kernel])
+    try:
+        nat._bls_check('pv_bls_verify_batch_device', lib.pv_bls_verify_batch_device(
+            _p(sig), _p(blob), _p(off), 2, _p(midx), _p(kidx), 6, _p(verdict), 0, _stream(dev)))
+    finally:
+        nat.set_tuning(**prev)
     assert verdict.cpu().tolist() == [1, 1, 0, 0, 0, 0]
 
 
