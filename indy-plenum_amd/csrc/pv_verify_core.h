@@ -488,17 +488,17 @@ PV_HD void ge_madd_entry(ge_p1p1& r, const ge_p3& p, const ge_nentry& e, bool ne
 // cached multiples 0..8 of P into a per-lane table (9 x 40 words)
 template <int LS = 1>
 PV_HD void build_atab(uint32_t* atab, const ge_p3& P) {
-  ge_cached c;
+  ge_cached c, c1;
   ge_cached_identity(c);
   store_cached<LS>(atab, c);
-  ge_p3_to_cached(c, P);
-  store_cached<LS>(atab + AT_ENTRY * LS, c);
+  ge_p3_to_cached(c1, P);
+  store_cached<LS>(atab + AT_ENTRY * LS, c1);
   ge_p3 prev = P;
+  // 1*P stays in registers (the loop has them to spare at 2 waves/SIMD): the
+  // loop only stores, so nothing in it waits for memory; the first wait after
+  // the build is the caller's first table read
 #pragma unroll 1
   for (int k = 2; k <= 8; ++k) {
-    // re-read 1*P from the table instead of keeping it live (register budget)
-    ge_cached c1;
-    load_cached<LS>(c1, atab + AT_ENTRY * LS);
     ge_p1p1 t;
     ge_add_cached(t, prev, c1, false);
     ge_p1p1_to_p3(prev, t);

@@ -43,6 +43,14 @@ KERNEL(lshrrev_b64, uint64_t, (uint64_t)(a + c), { asm volatile("v_lshrrev_b64 %
 KERNEL(mov_b32, uint32_t, a + c, { asm volatile("v_mov_b32 %0, %1" : "=v"(acc[c]) : "v"(acc[(c + 1) % CHAINS])); })
 KERNEL(cndmask_b32, uint32_t, a + c,
        { asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(acc[c]) : "v"(b) : "vcc"); })
+// fe_cmov's pattern: the per-lane boolean is a lane mask in an SGPR pair (not
+// vcc, which the row above leaves to whatever the prologue set) and the selects
+// of the ten limbs follow one another; and the mask form of the same select
+// (mask = 0 - flag in a VGPR, one v_bfi_b32 per limb)
+KERNEL(cndmask_b32_sgpr_mask, uint32_t, a + c,
+       { asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(acc[c]) : "v"(b), "s"(__ballot((a >> 3) & 1u))); })
+KERNEL(bfi_b32, uint32_t, a + c,
+       { asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(0u - ((a >> 3) & 1u)), "v"(b)); })
 KERNEL(mad_u32_u24, uint32_t, a + c, { asm volatile("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(a), "v"(b)); })
 
 typedef void (*kfn)(uint64_t*, uint32_t*, uint32_t);
@@ -53,6 +61,7 @@ int main() {
     {"v_and_b32", k_and_b32}, {"v_lshlrev_b32", k_lshlrev_b32}, {"v_add3_u32", k_add3_u32},
     {"v_alignbit_b32", k_alignbit_b32}, {"v_lshl_add_u64", k_lshl_add_u64}, {"v_lshrrev_b64", k_lshrrev_b64},
     {"v_mov_b32", k_mov_b32}, {"v_cndmask_b32", k_cndmask_b32}, {"v_mad_u32_u24", k_mad_u32_u24},
+    {"v_cndmask_b32 (SGPR-pair mask)", k_cndmask_b32_sgpr_mask}, {"v_bfi_b32", k_bfi_b32},
   };
   const int nk = sizeof(ks) / sizeof(ks[0]);
   int cus = 256;
