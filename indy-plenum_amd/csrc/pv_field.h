@@ -34,6 +34,10 @@
 #ifndef PV_CHECK_MUL
 #define PV_CHECK_MUL(f, g)
 #endif
+// fe_sub (k = 2) / fe_sub4 (k = 4): every limb of g at most the limb of k p
+#ifndef PV_CHECK_SUB
+#define PV_CHECK_SUB(g, k)
+#endif
 #ifndef PV_CHECK_SQ
 #define PV_CHECK_SQ(f)
 #endif
@@ -626,20 +630,45 @@ static constexpr uint32_t P2_0 = 2u * ((1u << 26) - 19);
 static constexpr uint32_t P2_E = 2u * ((1u << 26) - 1);
 static constexpr uint32_t P2_O = 2u * ((1u << 25) - 1);
 
-// h = f - g + 2p ; g must be TIGHT.  LOOSE result when f is TIGHT.
+// One limb of a biased subtraction, f + K - g with K the 2p / 4p limb.
+// PV_SUB_SAD (default 1): on the device it is ONE v_sad_u32, |K - g| + f with K
+// in an SGPR (VOP3 takes no literal on gfx9), instead of the v_sub_u32 +
+// v_add_u32 pair the plain expression compiles to.  The two forms agree only
+// for g <= K, which is fe_sub's / fe_sub4's contract below (the host
+// bound-checking build asserts it at every call, PV_CHECK_SUB).  The asm is
+// forced because the compiler folds the plain |K - g| + f back into sub + add
+// wherever it can prove g <= K.  -DPV_SUB_SAD=0 builds the pair for A/B timing.
+#ifndef PV_SUB_SAD
+#define PV_SUB_SAD 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PV_FE_NOASM) && PV_SUB_SAD
+__device__ __forceinline__ uint32_t sub_bias(uint32_t K, uint32_t g, uint32_t f) {
+  uint32_t r;
+  asm("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "s"(K), "v"(g), "v"(f));
+  return r;
+}
+#else
+PV_HD uint32_t sub_bias(uint32_t K, uint32_t g, uint32_t f) { return f + K - g; }
+#endif
+
+// h = f - g + 2p ; g <= 2p limb for limb (TIGHT implies it).  LOOSE result
+// when f is TIGHT.
 PV_HD void fe_sub(fe& h, const fe& f, const fe& g) {
   PV_COUNT(sub);
-  h.v[0] = f.v[0] + P2_0 - g.v[0];
+  PV_CHECK_SUB(g, 2);
+  h.v[0] = sub_bias(P2_0, g.v[0], f.v[0]);
 #pragma unroll
-  for (int i = 1; i < 10; ++i) h.v[i] = f.v[i] + ((i & 1) ? P2_O : P2_E) - g.v[i];
+  for (int i = 1; i < 10; ++i) h.v[i] = sub_bias((i & 1) ? P2_O : P2_E, g.v[i], f.v[i]);
 }
 
-// h = f - g + 4p ; g may be LOOSE up to 2^28 / 2^27.  Result needs fe_carry.
+// h = f - g + 4p ; g <= 4p limb for limb: limb 0 <= 2^28 - 76, even limbs
+// <= 2^28 - 4, odd limbs <= 2^27 - 4.  Result needs fe_carry.
 PV_HD void fe_sub4(fe& h, const fe& f, const fe& g) {
   PV_COUNT(sub);
-  h.v[0] = f.v[0] + 2u * P2_0 - g.v[0];
+  PV_CHECK_SUB(g, 4);
+  h.v[0] = sub_bias(2u * P2_0, g.v[0], f.v[0]);
 #pragma unroll
-  for (int i = 1; i < 10; ++i) h.v[i] = f.v[i] + 2u * ((i & 1) ? P2_O : P2_E) - g.v[i];
+  for (int i = 1; i < 10; ++i) h.v[i] = sub_bias(2u * ((i & 1) ? P2_O : P2_E), g.v[i], f.v[i]);
 }
 
 // -f = 2p - f (f TIGHT) -> LOOSE

@@ -75,6 +75,17 @@ static void hc_check_sq2x(const uint32_t* f) {
     if (s >> 64) hc_bad("column2x", k, (unsigned long long)(s >> 64));
   }
 }
+// fe_sub (k = 2) / fe_sub4 (k = 4): the device forms |K - g| + f and f + K - g
+// agree only while every limb of g is at most K, the limb of k p
+static uint64_t g_sub_checks = 0;
+static void hc_check_sub(const uint32_t* g, int k) {
+  ++g_sub_checks;
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t K = (uint64_t)k * (i == 0 ? (1u << 26) - 19 : (i & 1) ? (1u << 25) - 1 : (1u << 26) - 1);
+    if (g[i] > K) hc_bad(k == 2 ? "sub g > 2p" : "sub4 g > 4p", i, g[i]);
+  }
+}
+#define PV_CHECK_SUB(g, k) hc_check_sub((g).v, (k))
 #define PV_CHECK_MUL(f, g) hc_check_mul((f).v, (g).v)
 #define PV_CHECK_SQ2X(f) hc_check_sq2x((f).v)
 #define PV_CHECK_SQ(f) hc_check_sq((f).v)
@@ -387,7 +398,11 @@ void hc_btable(uint32_t* out) {
 void hc_reset_counts(void) {
   memset(g_cnt, 0, sizeof g_cnt);
   g_bad_bound = 0;
+  g_sub_checks = 0;
 }
+
+// subtrahend checks (fe_sub / fe_sub4 calls) since the last reset
+uint64_t hc_get_sub_checks(void) { return g_sub_checks; }
 
 // counts[0..7] = mul, sq, add, carry, sha blocks, scalar reductions, sub, even-limb carries
 int hc_get_counts(uint64_t* counts) {

@@ -52,6 +52,14 @@ KERNEL(cndmask_b32_sgpr_mask, uint32_t, a + c,
 KERNEL(bfi_b32, uint32_t, a + c,
        { asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(0u - ((a >> 3) & 1u)), "v"(b)); })
 KERNEL(mad_u32_u24, uint32_t, a + c, { asm volatile("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(acc[c]) : "v"(a), "v"(b)); })
+// fe_sub's limb, f + K - g with K the 2p / 4p limb: as |K - g| + f in one
+// v_sad_u32 with K in an SGPR (VOP3 takes no literal on gfx9), and as the
+// v_sub_u32 + v_add_u32 (32-bit literal) pair the plain expression compiles to.
+// The pair's row counts one PAIR as one "instruction".
+KERNEL(sad_u32_sgpr, uint32_t, a + c,
+       { asm volatile("v_sad_u32 %0, %1, %0, %2" : "+v"(acc[c]) : "s"(s + 0x7ffffdau), "v"(b)); })
+KERNEL(sub_add_pair, uint32_t, a + c,
+       { asm volatile("v_sub_u32 %0, %1, %0\n\tv_add_u32 %0, 0x7ffffda, %0" : "+v"(acc[c]) : "v"(b)); })
 
 typedef void (*kfn)(uint64_t*, uint32_t*, uint32_t);
 
@@ -62,6 +70,7 @@ int main() {
     {"v_alignbit_b32", k_alignbit_b32}, {"v_lshl_add_u64", k_lshl_add_u64}, {"v_lshrrev_b64", k_lshrrev_b64},
     {"v_mov_b32", k_mov_b32}, {"v_cndmask_b32", k_cndmask_b32}, {"v_mad_u32_u24", k_mad_u32_u24},
     {"v_cndmask_b32 (SGPR-pair mask)", k_cndmask_b32_sgpr_mask}, {"v_bfi_b32", k_bfi_b32},
+    {"v_sad_u32 (SGPR constant)", k_sad_u32_sgpr}, {"v_sub_u32 + v_add_u32 literal (pair)", k_sub_add_pair},
   };
   const int nk = sizeof(ks) / sizeof(ks[0]);
   int cus = 256;
