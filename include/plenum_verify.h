@@ -385,7 +385,8 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
  * sha3(rlp(node)) and never changes (state/trie/pruning_trie.py:346-353) -- and
  * Trie.generate_state_proof (:1043-1050, :1075-1098; PruningState.generate_state_proof,
  * state/pruning_state.py:105-106) is Trie._get (:376-407) from a root plus a record of every node
- * fetched by hash, with the root appended.  So the store only grows, and a proof at any committed
+ * fetched by hash, with the root appended.  So the store only grows between two
+ * pv_state_store_prune calls, and a proof at any committed
  * root, current or historical, is a walk over hash lookups.  One call replaces one
  * generate_state_proof(key, root, serialize=True, get_value=True) per reply of
  * ReadRequestHandler._get_value_from_state
@@ -438,9 +439,9 @@ int pv_state_proof_verify_device(const uint8_t *node_blob, const uint64_t *node_
  * _generate_state_proof has (pf.append(root), and the NOTE at :1102), the rest of the reference's
  * order is Python set order.  Blank root: the proof is the empty list, the one byte 0xc0, which
  * is what verify accepts; the reference would serialize [b''].
- * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal) and pruning of
- * nodes (building a trie from a batch: pv_state_build; sets onto a committed root:
- * pv_state_update; sets and removals: pv_state_apply). */
+ * Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal).  (Building a trie
+ * from a batch: pv_state_build; sets onto a committed root: pv_state_update; sets and removals:
+ * pv_state_apply; dropping the nodes no kept root reaches: pv_state_store_prune.) */
 #define PV_SP_PATH_TOO_LONG 4
 int pv_state_store_create(uint64_t node_hint, uint64_t byte_hint, int device, int32_t *store_out);
 int pv_state_store_add(int32_t store, const uint8_t *node_blob, const uint64_t *node_off, uint64_t n_new,
@@ -460,6 +461,60 @@ int pv_state_store_walk_device(int32_t store, const uint8_t *roots, const uint32
 int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const uint32_t *node_count,
                                uint32_t max_nodes, const uint64_t *proof_off, uint64_t n_queries,
                                uint8_t *proof_blob, void *stream);
+
+/* Pruning the store (csrc/pv_trie_prune.h): keep exactly the nodes reachable from the roots the
+ * caller names, drop the rest and give the memory back.  It replaces what the reference's pruning
+ * state does on commit and revertToHead (state/pruning_state.py:87-102): reference counts on every
+ * node (state/db/refcount_db.py), a death row of nodes whose count fell to zero and an epoch ttl
+ * after which they are deleted (state/trie/pruning_trie.py:208-230, 681).  The difference from the
+ * reference: no counts, no death row and no ttl -- reachability from NAMED roots.  A node calls it
+ * with committedHeadHash, the heads of its uncommitted batches and every root it still serves to
+ * readers; whatever else the store held (earlier roots, reverted batches, the duplicates
+ * pv_state_apply re-emits) is gone afterwards.
+ *   keep_roots    HOST memory, n_roots x 32 bytes.
+ *   root_status   (may be NULL; n_roots bytes, written in both modes) PV_SP_OK, or
+ *                 PV_SP_NODE_MISSING for a non-blank root the store does not hold.  The blank root
+ *                 is PV_SP_OK and reaches nothing.
+ *   apply == 0    the sizing and reporting call: every output is written, the store is untouched.
+ *   apply != 0    the store is compacted.
+ *   n_kept, bytes_kept, n_missing, kept_digests   each may be NULL.  n_missing counts the 32-byte
+ *                 child references of kept nodes that the store does not hold (a store filled from
+ *                 proofs is partial by design; a walk that needs such a node answered
+ *                 PV_SP_NODE_MISSING before and still does).  kept_digests has digest_cap entries of
+ *                 32 bytes and receives the kept nodes' digests in new-id order.
+ * The kept set is the closure of "a node some walk of pv_state_store_prove from a kept root can
+ * fetch by hash": the children of a branch's items 0 .. 15 and of an extension's item 1, through
+ * inline nodes; a 32-byte leaf value or branch value is never followed, and a node that is no trie
+ * node is kept when referenced and contributes no children.  So for every kept root r and key k
+ * pv_state_store_prove(r, k) returns the same status, node_count, value and proof bytes as before,
+ * and pv_state_apply / pv_state_update onto a kept root return the same root and nodes.
+ * After apply != 0: the kept nodes are renumbered in ascending order of their old ids (a stable
+ * compaction: the result depends on the store's content and the roots alone); duplicate ids and
+ * their dead bytes are gone, n_nodes == n_unique == n_kept and n_bytes == bytes_kept; the table is
+ * rebuilt at the smallest power of two >= max(64, 2 n_kept); the node and byte capacities shrink to
+ * the next power of two that holds the kept data.  NODE IDS HANDED OUT EARLIER
+ * (pv_state_store_walk_device) ARE INVALID.  The new buffers are built beside the old ones and
+ * swapped in at the end: a failure leaves the store as it was.  Synchronous and ordered like every
+ * other store call.
+ * Refusals, each before any change to the store: PV_EINVAL for an unknown store, n_roots == 0 (free
+ * the store instead), keep_roots == NULL, kept_digests with digest_cap < n_kept (the text starts
+ * "digest capacity too small" and *n_kept holds the need), with apply != 0 any root that is
+ * PV_SP_NODE_MISSING (a mistyped root must not empty a store; the text names its index and
+ * root_status is written), and inline nodes nested more than 7 deep under a stored node (a
+ * well-formed trie nests 3 deep; only junk added with pv_state_store_add goes deeper).
+ * PV_ENOTINIT without pv_init; PV_ENOMEM when the fresh buffers cannot be allocated.
+ *   pv_state_store_prune (state/pruning_state.py:87-102; pruning_trie.py:681; refcount_db.py) */
+int pv_state_store_prune(int32_t store, const uint8_t *keep_roots, uint64_t n_roots, int apply,
+                         uint8_t *root_status, uint64_t *n_kept, uint64_t *bytes_kept, uint64_t *n_missing,
+                         uint8_t *kept_digests, uint64_t digest_cap);
+
+/* Time the phases of one applied prune (pv_state_store_prune with apply != 0, same refusals, the
+ * store is compacted) with HIP events on the store's stream, as pv_time_verify_device times the
+ * verify kernels: *ms_mark = the seed kernel and the level loop with its count read-backs,
+ * *ms_compact = the keep flags, the two scans, the allocation of the fresh buffers and the copy,
+ * *ms_rehash = clearing and refilling the fresh table.  For tools/bench_state_prune.py. */
+int pv_time_state_store_prune(int32_t store, const uint8_t *keep_roots, uint64_t n_roots, uint64_t *n_kept,
+                              uint64_t *bytes_kept, float *ms_mark, float *ms_compact, float *ms_rehash);
 
 /* Batch construction of a state trie (csrc/pv_trie_build.h): the write side of the store above.
  * The reference computes a state root with one PruningState.set per key and reads headHash
@@ -517,7 +572,7 @@ int pv_state_build_device(const uint8_t *key_blob, const uint64_t *key_off, cons
  * walks the old trie in `store` from old_root and carries, as it is, the reference of every
  * child no batch key enters; the carried values and references and the new values make one
  * sorted list, and the build above runs over it.  No host trie and no other key of the state is
- * needed, and every earlier root stays provable: the store only grows.
+ * needed, and every earlier root stays provable: an update only adds to the store.
  *   Input    store: where the old trie is read.  old_root (32 bytes, HOST memory in both forms).
  *            Keys and values as pv_state_build[_device].
  *   insert   != 0: the emitted nodes are appended to `store` with the digests the build computed.
@@ -547,8 +602,8 @@ int pv_state_build_device(const uint8_t *key_blob, const uint64_t *key_off, cons
  *   pv_state_update_device (state/pruning_state.py:60-61; pruning_trie.py:1006-1027)
  *            DEVICE buffers (node outputs too), keys strictly increasing, on the store's device.
  * Calls are synchronous and ordered on the store's stream (NULL = the library's).  Sets only: an
- * empty value is refused; removals go through pv_state_apply below.  Out of scope: pruning of
- * nodes no root reaches. */
+ * empty value is refused; removals go through pv_state_apply below.  The nodes an update leaves
+ * unreachable go with pv_state_store_prune. */
 int pv_state_update(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
                     const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
                     uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,
@@ -584,7 +639,7 @@ int pv_state_update_device(int32_t store, const uint8_t *old_root, const uint8_t
  *            an earlier set and the other way round.
  *   pv_state_apply_device (state/pruning_state.py:60-61, 84-85; pruning_trie.py:683-848, 1006-1027)
  *            DEVICE buffers (node outputs too), keys strictly increasing, on the store's device.
- * Out of scope: pruning of nodes no root reaches (the store only grows). */
+ * The store grows with every batch; pv_state_store_prune drops the nodes no kept root reaches. */
 int pv_state_apply(int32_t store, const uint8_t *old_root, const uint8_t *key_blob, const uint64_t *key_off,
                    const uint8_t *val_blob, const uint64_t *val_off, uint64_t n, int insert, uint8_t *new_root,
                    uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off,

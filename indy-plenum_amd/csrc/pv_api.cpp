@@ -27,6 +27,7 @@
 #include "pv_kernels.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
+#include "pv_trie_prune.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
 
@@ -3159,6 +3160,193 @@ int pv_state_store_prove(int32_t store, const uint8_t* roots, const uint32_t* ro
                                     dpoff.p, n_queries, dproof.p, merkle_blocks(d), s));
   HIP_OK(hipMemcpyAsync(proof_blob, dproof.p, total, hipMemcpyDeviceToHost, s));
   return tail.finish();
+}
+
+}  // extern "C"
+
+namespace {
+
+// the buffers a prune builds beside the store's own: freed unless the swap took them
+struct FreshStore {
+  uint8_t* blob = nullptr;
+  uint64_t *beg = nullptr, *end = nullptr;
+  uint32_t *dig = nullptr, *table = nullptr;
+  uint8_t* dup = nullptr;
+  unsigned int* unique = nullptr;
+  bool taken = false;
+  ~FreshStore() {
+    if (taken) return;
+    void* bufs[] = {blob, beg, end, dig, table, dup, unique};
+    for (void* p : bufs)
+      if (p) (void)hipFree(p);
+  }
+};
+
+template <typename T>
+hipError_t fresh_alloc(T** p, uint64_t n) {
+  return hipMalloc(reinterpret_cast<void**>(p), (size_t)n * sizeof(T));
+}
+
+// HIP events at the phase boundaries of a timed prune (pv_time_state_store_prune)
+struct PhaseEvents {
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool on = false;
+  hipError_t create() {
+    on = true;
+    for (auto& e : ev)
+      if (const hipError_t rc = hipEventCreate(&e)) return rc;
+    return hipSuccess;
+  }
+  hipError_t mark(int i, hipStream_t s) { return on ? hipEventRecord(ev[i], s) : hipSuccess; }
+  ~PhaseEvents() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// pv_state_store_prune; phase_ms (NULL, or 3 floats: mark, scans + copy, rehash of an applied prune)
+int prune_impl(int32_t store, const uint8_t* keep_roots, uint64_t n_roots, int apply, uint8_t* root_status,
+               uint64_t* n_kept, uint64_t* bytes_kept, uint64_t* n_missing, uint8_t* kept_digests,
+               uint64_t digest_cap, float* phase_ms) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_roots == 0) return fail(PV_EINVAL, "no root to keep (free the store instead)");
+  if (!keep_roots) return fail(PV_EINVAL, "null buffer");
+  if (n_roots > (1ull << 31)) return fail(PV_EINVAL, "more than 2^31 roots to keep");
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  hipStream_t s = en.s;
+  const int mb = merkle_blocks(d);
+  const uint64_t n = st->n_nodes, words = (n + 31) / 32;
+  TmpBuf<uint8_t> droots, dstatus;
+  TmpBuf<uint32_t> bits, queue, ddig;
+  TmpBuf<unsigned long long> counts;
+  TmpBuf<uint64_t> keep, len;
+  FreshStore f;
+  PhaseEvents ph;
+  StreamDrain tail{s};
+  if (phase_ms) HIP_OK(ph.create());
+  HIP_OK(ph.mark(0, s));
+  // mark: the roots, then one launch per level until a level appends nothing
+  HIP_OK(droots.put(keep_roots, n_roots * 32, s));
+  HIP_OK(dstatus.alloc(n_roots));
+  HIP_OK(bits.alloc(words));
+  if (words) HIP_OK(hipMemsetAsync(bits.p, 0, words * 4, s));
+  HIP_OK(queue.alloc(st->n_unique));   // an id is enqueued by the lane that flipped its bit: at most once
+  HIP_OK(counts.alloc(pv::TP_COUNTS));
+  HIP_OK(hipMemsetAsync(counts.p, 0, pv::TP_COUNTS * 8, s));
+  const pv::TpCtx c{st->blob, st->beg,  st->end, st->dig,  st->table, st->slots,
+                    (uint32_t)n, bits.p, queue.p, counts.p};
+  HIP_OK(pv::launch_trie_prune_seed(c, w32(droots.p), n_roots, dstatus.p, mb, s));
+  unsigned long long hc[pv::TP_COUNTS] = {0, 0, 0};
+  for (uint64_t head = 0;;) {
+    HIP_OK(hipMemcpyAsync(hc, counts.p, sizeof hc, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (hc[pv::TP_TAIL] > st->n_unique) return fail(PV_EIO, "state prune: the mark queue overran the store");
+    if (hc[pv::TP_TAIL] == head) break;   // each level marks at least one new node, or ends the loop
+    HIP_OK(pv::launch_trie_prune_level(c, head, hc[pv::TP_TAIL], mb, s));
+    head = hc[pv::TP_TAIL];
+  }
+  const uint64_t kept = hc[pv::TP_TAIL];
+  HIP_OK(ph.mark(1, s));
+  std::vector<uint8_t> hstat(n_roots);
+  HIP_OK(hipMemcpyAsync(hstat.data(), dstatus.p, n_roots, hipMemcpyDeviceToHost, s));
+  // new ids and new byte offsets: two exclusive scans over the keep flags and the kept lengths
+  HIP_OK(keep.alloc(n + 1));
+  HIP_OK(len.alloc(n + 1));
+  HIP_OK(pv::launch_trie_prune_flags(bits.p, st->beg, st->end, n, keep.p, len.p, mb, s));
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(n + 1)));
+  HIP_OK(pv::launch_exclusive_scan(keep.p, n + 1, d.scan.p, s));
+  HIP_OK(pv::launch_exclusive_scan(len.p, n + 1, d.scan.p, s));
+  uint64_t bytes = 0;
+  HIP_OK(hipMemcpyAsync(&bytes, len.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (root_status) memcpy(root_status, hstat.data(), n_roots);
+  if (hc[pv::TP_OVERFLOW])
+    return fail(PV_EINVAL, "state prune: inline nodes nest more than %d deep under a stored node", pv::TP_MAX_INLINE);
+  if (n_kept) *n_kept = kept;
+  if (bytes_kept) *bytes_kept = bytes;
+  if (n_missing) *n_missing = hc[pv::TP_MISSING];
+  if (apply)
+    for (uint64_t i = 0; i < n_roots; ++i)
+      if (hstat[i] != PV_SP_OK)
+        return fail(PV_EINVAL, "state prune: keep root %llu is not in the store", (unsigned long long)i);
+  if (kept_digests && digest_cap < kept)
+    return fail(PV_EINVAL, "digest capacity too small: %llu entries for %llu kept nodes",
+                (unsigned long long)digest_cap, (unsigned long long)kept);
+  if (!apply) {   // the reporting call: the store stays as it is
+    if (kept_digests && kept) {
+      HIP_OK(ddig.alloc(kept * 8));
+      HIP_OK(pv::launch_trie_prune_copy(st->blob, st->beg, st->end, st->dig, bits.p, keep.p, len.p, n, nullptr,
+                                        nullptr, nullptr, ddig.p, mb, s));
+      HIP_OK(hipMemcpyAsync(kept_digests, ddig.p, kept * 32, hipMemcpyDeviceToHost, s));
+    }
+    return tail.finish();
+  }
+  // compact into fresh buffers beside the old ones; the swap is the last step
+  const uint64_t cap_nodes = pv::tp_pow2(kept, 1), cap_bytes = pv::tp_pow2(bytes, 1);
+  const uint64_t slots = pv::tp_pow2(2 * kept, pv::TS_MIN_SLOTS);   // kept <= n_unique <= 2^30
+  HIP_OK(fresh_alloc(&f.blob, cap_bytes + 16));
+  HIP_OK(fresh_alloc(&f.beg, cap_nodes));
+  HIP_OK(fresh_alloc(&f.end, cap_nodes));
+  HIP_OK(fresh_alloc(&f.dig, cap_nodes * 8));
+  HIP_OK(fresh_alloc(&f.dup, cap_nodes));
+  HIP_OK(fresh_alloc(&f.table, slots));
+  HIP_OK(fresh_alloc(&f.unique, 1));
+  HIP_OK(pv::launch_trie_prune_copy(st->blob, st->beg, st->end, st->dig, bits.p, keep.p, len.p, n, f.blob, f.beg,
+                                    f.end, f.dig, mb, s));
+  HIP_OK(hipMemsetAsync(f.blob + bytes, 0, 16, s));
+  HIP_OK(ph.mark(2, s));
+  HIP_OK(hipMemsetAsync(f.dup, 0, cap_nodes, s));
+  HIP_OK(hipMemsetAsync(f.table, 0, slots * 4, s));
+  HIP_OK(pv::launch_trie_store_rehash(f.table, (uint32_t)slots, f.dig, f.dup, (uint32_t)kept, mb, s));
+  HIP_OK(ph.mark(3, s));
+  if (kept_digests && kept) HIP_OK(hipMemcpyAsync(kept_digests, f.dig, kept * 32, hipMemcpyDeviceToHost, s));
+  const unsigned int uniq = (unsigned int)kept;
+  HIP_OK(hipMemcpyAsync(f.unique, &uniq, 4, hipMemcpyHostToDevice, s));
+  if (const int rc = tail.finish()) return rc;
+  if (phase_ms)
+    for (int i = 0; i < 3; ++i) HIP_OK(hipEventElapsedTime(phase_ms + i, ph.ev[i], ph.ev[i + 1]));
+  void* old[] = {st->blob, st->beg, st->end, st->dig, st->dup, st->table, st->unique};
+  for (void* p : old)
+    if (p) (void)hipFree(p);
+  f.taken = true;
+  st->blob = f.blob;
+  st->beg = f.beg;
+  st->end = f.end;
+  st->dig = f.dig;
+  st->dup = f.dup;
+  st->table = f.table;
+  st->unique = f.unique;
+  st->cap_bytes = cap_bytes;
+  st->cap_nodes = cap_nodes;
+  st->slots = (uint32_t)slots;
+  st->n_nodes = st->n_unique = kept;
+  st->n_bytes = bytes;
+  return PV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pv_state_store_prune(int32_t store, const uint8_t* keep_roots, uint64_t n_roots, int apply, uint8_t* root_status,
+                         uint64_t* n_kept, uint64_t* bytes_kept, uint64_t* n_missing, uint8_t* kept_digests,
+                         uint64_t digest_cap) {
+  return prune_impl(store, keep_roots, n_roots, apply, root_status, n_kept, bytes_kept, n_missing, kept_digests,
+                    digest_cap, nullptr);
+}
+
+int pv_time_state_store_prune(int32_t store, const uint8_t* keep_roots, uint64_t n_roots, uint64_t* n_kept,
+                              uint64_t* bytes_kept, float* ms_mark, float* ms_compact, float* ms_rehash) {
+  if (!ms_mark || !ms_compact || !ms_rehash) return fail(PV_EINVAL, "null pointer");
+  float ms[3] = {0, 0, 0};
+  const int rc = prune_impl(store, keep_roots, n_roots, 1, nullptr, n_kept, bytes_kept, nullptr, nullptr, 0, ms);
+  *ms_mark = ms[0];
+  *ms_compact = ms[1];
+  *ms_rehash = ms[2];
+  return rc;
 }
 
 }  // extern "C"

@@ -230,6 +230,24 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
                                   const uint64_t* proof_off, uint64_t n_queries, uint8_t* proof_blob, int max_blocks,
                                   hipStream_t s);
 
+// Pruning the resident store (pv_trie_prune.h); all device memory.
+//   trie_prune_seed   one lane per kept root: status[i], the root's node marked and enqueued
+//   trie_prune_level  one lane per queue entry head .. tail - 1: tp_expand (children marked, the
+//                     newly marked ones appended at c.counts[TP_TAIL])
+//   trie_prune_flags  keep[i] / len[i], i = 0 .. n (0 at n): what the two exclusive scans take
+//   trie_prune_copy   one wave per old id: a marked one to new id keep[i] at byte off[i] (scanned);
+//                     nblob == nullptr: the digests alone
+struct TpCtx;
+hipError_t launch_trie_prune_seed(const TpCtx& c, const uint32_t* roots, uint64_t n_roots, uint8_t* status,
+                                  int max_blocks, hipStream_t s);
+hipError_t launch_trie_prune_level(const TpCtx& c, uint64_t head, uint64_t tail, int max_blocks, hipStream_t s);
+hipError_t launch_trie_prune_flags(const uint32_t* bits, const uint64_t* beg, const uint64_t* end, uint64_t n,
+                                   uint64_t* keep, uint64_t* len, int max_blocks, hipStream_t s);
+hipError_t launch_trie_prune_copy(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                                  const uint32_t* bits, const uint64_t* keep, const uint64_t* off, uint64_t n,
+                                  uint8_t* nblob, uint64_t* nbeg, uint64_t* nend, uint32_t* ndig, int max_blocks,
+                                  hipStream_t s);
+
 // Batch trie build (pv_trie_build.h); all device memory.  One item per lane of the routine
 // named: tb_lcp_one over positions 0 .. n (stats[0] <- max h by atomicMax, stats[1 .. 3] <- the
 // first index refused for order / value / offsets by atomicMin), tb_min_one over the `size`

@@ -19,6 +19,7 @@
 #include "pv_sha3.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
+#include "pv_trie_prune.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
 #include "pv_kernels.h"
@@ -1930,6 +1931,92 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
   if (n_queries == 0) return hipSuccess;
   hipLaunchKernelGGL(k_trie_proof_pack, dim3(mp_grid(n_queries * 64, max_blocks)), dim3(256), 0, s, blob, beg,
                      end, n_nodes, node_ids, node_count, max_nodes, proof_off, n_queries, proof_blob);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- pruning the resident store
+// pv_trie_prune.h.  Mark: one lane per kept root, then per level one lane per
+// queue entry of the window the level before appended; no kernel waits on
+// another workgroup.  status[i] = SP_OK / SP_NODE_MISSING of root i.
+__global__ __launch_bounds__(256) void k_trie_prune_seed(TpCtx c, const uint32_t* __restrict__ roots,
+                                                          uint64_t n_roots, uint8_t* __restrict__ status) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_roots; i += stride) {
+    uint32_t rt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) rt[k] = roots[8 * i + k];
+    status[i] = (uint8_t)tp_seed(c, rt);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_trie_prune_level(TpCtx c, uint64_t head, uint64_t tail) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t q = head + (uint64_t)blockIdx.x * 256 + threadIdx.x; q < tail; q += stride) tp_expand(c, q);
+}
+
+// keep[i] = 1 and len[i] = the byte length of every marked id, 0 for the others
+// and for i = n: the inputs of the two exclusive scans (new id, new offset)
+__global__ __launch_bounds__(256) void k_trie_prune_flags(const uint32_t* __restrict__ bits,
+                                                           const uint64_t* __restrict__ beg,
+                                                           const uint64_t* __restrict__ end, uint64_t n,
+                                                           uint64_t* __restrict__ keep, uint64_t* __restrict__ len) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i <= n; i += stride) {
+    const bool k = i < n && tp_marked(bits, (uint32_t)i);
+    keep[i] = k ? 1 : 0;
+    len[i] = k ? end[i] - beg[i] : 0;
+  }
+}
+
+// One wave per old id; a marked one moves to id keep[i] at byte off[i] of the
+// new buffers: bytes as k_trie_proof_pack, the range and the 8 digest words.
+// nblob == nullptr: the digests alone (the reporting call).
+__global__ __launch_bounds__(256) void k_trie_prune_copy(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ beg, const uint64_t* __restrict__ end,
+    const uint32_t* __restrict__ dig, const uint32_t* __restrict__ bits, const uint64_t* __restrict__ keep,
+    const uint64_t* __restrict__ off, uint64_t n, uint8_t* __restrict__ nblob, uint64_t* __restrict__ nbeg,
+    uint64_t* __restrict__ nend, uint32_t* __restrict__ ndig) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t i = wave; i < n; i += waves) {
+    if (!tp_marked(bits, (uint32_t)i)) continue;
+    const uint64_t j = keep[i];
+    if (lane < 8) ndig[8 * j + lane] = dig[8 * i + lane];
+    if (!nblob) continue;
+    const uint64_t b = beg[i], len = end[i] - b, o = off[i];
+    for (uint64_t x = lane; x < len; x += 64) nblob[o + x] = blob[b + x];
+    if (lane == 8) nbeg[j] = o;
+    if (lane == 9) nend[j] = o + len;
+  }
+}
+
+hipError_t launch_trie_prune_seed(const TpCtx& c, const uint32_t* roots, uint64_t n_roots, uint8_t* status,
+                                  int max_blocks, hipStream_t s) {
+  if (n_roots == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_prune_seed, dim3(mp_grid(n_roots, max_blocks)), dim3(256), 0, s, c, roots, n_roots, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_prune_level(const TpCtx& c, uint64_t head, uint64_t tail, int max_blocks, hipStream_t s) {
+  if (tail <= head) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_prune_level, dim3(mp_grid(tail - head, max_blocks)), dim3(256), 0, s, c, head, tail);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_prune_flags(const uint32_t* bits, const uint64_t* beg, const uint64_t* end, uint64_t n,
+                                   uint64_t* keep, uint64_t* len, int max_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_trie_prune_flags, dim3(mp_grid(n + 1, max_blocks)), dim3(256), 0, s, bits, beg, end, n, keep,
+                     len);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_prune_copy(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                                  const uint32_t* bits, const uint64_t* keep, const uint64_t* off, uint64_t n,
+                                  uint8_t* nblob, uint64_t* nbeg, uint64_t* nend, uint32_t* ndig, int max_blocks,
+                                  hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_prune_copy, dim3(mp_grid(n * 64, max_blocks)), dim3(256), 0, s, blob, beg, end, dig, bits,
+                     keep, off, n, nblob, nbeg, nend, ndig);
   return hipGetLastError();
 }
 

@@ -4,8 +4,10 @@
 // (state/trie/pruning_trie.py:346-353, _decode_to_node -> _db.get(hash)), and
 // generate_state_proof (:1043-1050, :1075-1098) is Trie._get (:376-407) from a
 // root plus a record of every node it fetched by hash, with the root appended.
-// So the store only grows ("add these node RLPs") and a proof at any committed
-// root, current or historical, is a walk over hash lookups.
+// So the store only grows ("add these node RLPs") between two prunes
+// (pv_trie_prune.h: keep what the named roots reach, renumber, rebuild the
+// table) and a proof at any root it holds, current or historical, is a walk
+// over hash lookups.
 //
 // Layout.  Node id j is the byte range blob[beg[j], end[j]) of one blob, its
 // SHA3-256 digest is dig[8 j .. 8 j + 7] (little-endian words, from

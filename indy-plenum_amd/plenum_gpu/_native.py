@@ -107,6 +107,12 @@ SIGNATURES = [
     ('pv_state_store_add_device', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     ('pv_state_store_info', ctypes.c_int, [ctypes.c_int32] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
     ('pv_state_store_free', ctypes.c_int, [ctypes.c_int32]),
+    ('pv_state_store_prune', ctypes.c_int,
+     [ctypes.c_int32, _vp, ctypes.c_uint64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_uint64),
+      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp, ctypes.c_uint64]),
+    ('pv_time_state_store_prune', ctypes.c_int,
+     [ctypes.c_int32, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)] +
+     [ctypes.POINTER(ctypes.c_float)] * 3),
     # root: a typed out-parameter (32 bytes of HOST memory in both forms)
     ('pv_state_build', ctypes.c_int,
      [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64),

@@ -52,8 +52,14 @@ reference would return [b''].
   the nodes referenced from the branches on its path in the store, where the reference decodes a
   sibling only on a collapse.  `update_state` and `build_state` keep refusing an empty value.
 
-Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal) and
-pruning of nodes no root reaches.
+* `GpuStateStore.prune(keep_roots)` / `reachable(roots)` -- pv_state_store_prune: keep exactly the
+  nodes some walk from a kept root can fetch by hash (csrc/pv_trie_prune.h), drop the rest --
+  earlier roots, reverted batches, the duplicates apply_batch re-emits -- and shrink the buffers.
+  The reference prunes by reference counts, a death row and an epoch ttl
+  (state/trie/pruning_trie.py:208-230, 681; state/db/refcount_db.py); here the caller names the
+  roots.  `reachable_host(db, roots)` is the pure-Python mirror of the mark.
+
+Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal).
 """
 import ctypes
 import hashlib
@@ -192,6 +198,76 @@ def walk_host(db, root, key, max_nodes=None):
         nodes.append(blob)
         cb, ce = 0, len(blob)
     return end(PV_SP_MALFORMED)
+
+
+def _node_children(blob, cb, ce, depth=0):
+    """The mark rule of csrc/pv_trie_prune.h for the node RLP blob[cb:ce] -> (the 32-byte child
+    references in item order, through inline nodes; the deepest inline nesting met).  A node that
+    does not parse at its own level has no children."""
+    head = _rlp_item(blob, cb, ce)
+    if head is None or not head[0] or head[2] != ce:
+        return [], depth
+    items, pos = [], head[1]
+    while pos < ce:
+        if len(items) == 17:
+            return [], depth
+        it = _rlp_item(blob, pos, ce)
+        if it is None:
+            return [], depth
+        items.append((pos,) + it)          # (start, is_list, payload begin, payload end)
+        pos = it[2]
+    if len(items) == 2:
+        _, i0l, i0b, i0e = items[0]
+        if i0l or i0e == i0b:
+            return [], depth
+        flags = blob[i0b] >> 4
+        if flags & 2 or 2 * (i0e - i0b - 1) + (flags & 1) == 0:
+            return [], depth               # a leaf's item 1 is its value; an extension over no nibble
+        children = [items[1]]
+    elif len(items) == 17:
+        children = items[:16]              # item 16 is a value, never a reference
+    else:
+        return [], depth
+    refs, deepest = [], depth
+    for start, is_list, pb, pe in children:
+        if is_list:                        # an inline node, visited in place
+            r, d = _node_children(blob, start, pe, depth + 1)
+            refs += r
+            deepest = max(deepest, d)
+        elif pe - pb == 32:
+            refs.append(bytes(blob[pb:pe]))
+    return refs, deepest
+
+
+def reachable_host(db, roots):
+    """The mark of csrc/pv_trie_prune.h in Python over `db` = {sha3(node RLP): node RLP}: the nodes
+    some walk_host from one of `roots` can fetch by hash -> (set of their digests, n_missing: the
+    child references of those nodes that db does not hold, each occurrence counted, [status per
+    root]: PV_SP_OK, or PV_SP_NODE_MISSING for a non-blank root db does not hold, the deepest inline
+    nesting met).  The blank root reaches nothing.  A 32-byte value is never followed."""
+    kept, queue, statuses = set(), [], []
+    for root in roots:
+        root = bytes(root)
+        if root == BLANK_ROOT or root in db:
+            statuses.append(PV_SP_OK)
+            if root != BLANK_ROOT and root not in kept:
+                kept.add(root)
+                queue.append(root)
+        else:
+            statuses.append(PV_SP_NODE_MISSING)
+    n_missing, deepest, at = 0, 0, 0
+    while at < len(queue):
+        blob = db[queue[at]]
+        at += 1
+        refs, d = _node_children(blob, 0, len(blob))
+        deepest = max(deepest, d)
+        for h in refs:
+            if h not in db:
+                n_missing += 1
+            elif h not in kept:
+                kept.add(h)
+                queue.append(h)
+    return kept, n_missing, statuses, deepest
 
 
 def _hex_prefix(nibbles, leaf):
@@ -715,7 +791,8 @@ class Proved:
 
 
 class GpuStateStore:
-    """A device-resident, append-only store of trie nodes keyed by their SHA3-256."""
+    """A device-resident store of trie nodes keyed by their SHA3-256: append-only between two
+    prune() calls, each of which keeps the nodes reachable from the roots it is given."""
 
     def __init__(self, device=0, node_hint=1 << 16, byte_hint=0):
         nat.ensure_init()
@@ -757,6 +834,53 @@ class GpuStateStore:
         if want_digests:
             return added.value, [dig[i].tobytes() for i in range(len(nodes))]
         return added.value
+
+    def _prune(self, roots, apply, want_digests):
+        roots = [root_hash_of(r) for r in roots]
+        if not roots:
+            raise ValueError('no root to keep: close the store instead')
+        rts = np.frombuffer(b''.join(roots), np.uint8)
+        status = np.zeros(len(roots), np.uint8)
+        kept, nbytes, missing = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+        def call(ap, dig, cap):
+            rc = self._lib.pv_state_store_prune(self._id, _p(rts), len(roots), ap, _p(status), ctypes.byref(kept),
+                                                ctypes.byref(nbytes), ctypes.byref(missing), _p(dig), cap)
+            if rc != 0 and (status == PV_SP_NODE_MISSING).any():
+                text = self._lib.pv_last_error().decode(errors='replace')
+                if 'is not in the store' in text:
+                    raise KeyError(text)
+            nat._check('pv_state_store_prune', rc)
+        dig = None
+        if want_digests or not apply:
+            call(0, None, 0)                           # the sizing call
+        if want_digests:
+            dig = np.zeros((max(kept.value, 1), 32), np.uint8)
+        if apply or want_digests:
+            call(apply, dig, kept.value if want_digests else 0)
+        out = {'n_kept': kept.value, 'bytes_kept': nbytes.value, 'n_missing': missing.value,
+               'root_status': [int(x) for x in status]}
+        if want_digests:
+            out['digests'] = [dig[i].tobytes() for i in range(kept.value)]
+        return out
+
+    def reachable(self, roots, want_digests=False):
+        """What a prune to `roots` (32-byte hashes or decoded root nodes, as root_hash_of takes them)
+        would keep; the store is untouched (pv_state_store_prune with apply == 0) -> {'n_kept',
+        'bytes_kept', 'n_missing': child references of kept nodes the store does not hold,
+        'root_status': PV_SP_OK or PV_SP_NODE_MISSING per root[, 'digests': the kept nodes' in new-id
+        order]}.  A root that is not in the store is reported, not refused."""
+        return self._prune(roots, 0, want_digests)
+
+    def prune(self, keep_roots, want_digests=False):
+        """Keep exactly the nodes reachable from `keep_roots`, drop the rest and give the memory back
+        (pv_state_store_prune) -> the dict of reachable(), after the compaction.  What the
+        reference's pruning state does with reference counts on commit and revertToHead
+        (state/pruning_state.py:87-102).  Keep committedHeadHash, the heads of uncommitted batches
+        and every root still served to readers: proofs and updates at a kept root are unchanged,
+        every other root is gone.  KeyError for a root that is not in the store (nothing is
+        dropped)."""
+        return self._prune(keep_roots, 1, want_digests)
 
     def build_state(self, items):
         """Build the trie of (key, raw value) pairs on the device (pv_state_build) and insert its
