@@ -71,6 +71,10 @@ def _random_ragged_vs_oracle(nat):
                          dtype=np.uint8).tobytes() for _ in range(n)]
     blob, off = nat.pack_messages(msgs)
     pk, sig = nat.sign_batch_arrays(seeds, blob, off)
+    # the GPU signer against the oracle's: a signer that hashed wrongly at some
+    # length would otherwise only move a row from accepted to rejected on both sides
+    pk_o, sig_o = orc.sign_batch(seeds, blob, off)
+    assert (pk == pk_o).all() and (sig == sig_o).all()
     # corrupt ~10 %: random bit anywhere in R, S or M
     for i in rng.choice(n, n // 10, replace=False):
         which = rng.integers(0, 3)
