@@ -32,6 +32,35 @@ def test_sha256_block_loader_vs_hashlib():
             assert out[i].tobytes() == hashlib.sha256(pre + m).digest(), (prefix, len(m))
 
 
+def test_sha256_length_misalignment_prefix_grid():
+    """tests/_merkle_device.py sha_grid (what the device-buffer GPU test feeds
+    pv_sha256_batch_device): every length at every start offset mod 4, a 0xff
+    tail of the documented 16 bytes, the blob itself at base + 0..3, four
+    prefixes -- through the kernels' block loader on the host"""
+    import _merkle_device as md
+    hc = _load()
+    msgs, placed = md.sha_grid()
+    blob, off = md.pack(msgs)
+    assert len(msgs) == 568 and 44000 < len(blob) < 44500 and blob[-16:].tobytes() == b'\xff' * 16
+    assert int(off[-1]) + 16 == len(blob)
+    assert sorted((ln, r) for _, ln, r in placed) == sorted((ln, r) for ln in md.SHA_LENGTHS for r in range(4))
+    for i, ln, r in placed:
+        assert len(msgs[i]) == ln and int(off[i]) % 4 == r
+    assert all(1 <= len(m) <= 3 for i, m in enumerate(msgs) if i not in {p[0] for p in placed})
+    batches = [msgs, md.long_message()] + md.last_message_batches()
+    assert [len(b[-1]) for b in batches[2:]] == [0, 1, 55, 56, 63, 64]
+    for batch in batches:
+        blob, off = md.pack(batch)
+        for prefix in (-1, 0x00, 0x01, 0xff):
+            want = md.sha_want(batch, prefix)
+            for k in range(4):
+                view = md.at_misalignment(blob, k)
+                out = np.zeros((len(batch), 32), np.uint8)
+                hc.hc_sha256(_p(view), _p(off), ctypes.c_uint64(len(batch)), ctypes.c_int(prefix), _p(out))
+                for i, m in enumerate(batch):
+                    assert out[i].tobytes() == want[i], (prefix, k, i, len(m))
+
+
 def test_sha256_node_vs_hashlib():
     hc = _load()
     for _ in range(50):

@@ -206,6 +206,121 @@ def test_header_routines_generate_the_fixture_paths_and_proofs(lib, fx, tree):
         lib.mc_tree_free(t)
 
 
+def test_walk_restatements_give_the_fixture_verdicts(lib, fx, tree):
+    """tests/_merkle_device.py ref_inclusion / ref_consistency (the expectation
+    of the device-buffer GPU tests' class tables) on every fixture row: the
+    fixture's verdict, and what the header's routines leave in their outputs"""
+    import _merkle_device as md
+    for r in fx['audit_paths']:
+        rt = bytes.fromhex(fx['roots'][str(r['s'])])
+        assert md.ref_inclusion(tree.lv[0][r['m']], r['m'], r['s'], mp.unhex(r['path']), rt) == (mp.OK, rt, 0)
+    for r in fx['neg_inclusion'] + fx['wide']:
+        if mp.negative(r):
+            continue
+        args = (bytes.fromhex(r['leaf_hash']), r['index'], r['tree_size'], mp.unhex(r['path']),
+                bytes.fromhex(r['root']))
+        got = md.ref_inclusion(*args)
+        want = mp.expect_inclusion(r)
+        assert all(w is None or w == g for w, g in zip(want, got)), r['what']
+        assert got == host_inclusion(lib, *args), r['what']
+    for r in fx['consistency']:
+        a, b = r['a'], r['b']
+        rb = bytes.fromhex(fx['roots'][str(b)])
+        ra = bytes.fromhex(fx['roots'][str(a)]) if a else rb
+        assert md.ref_consistency(a, b, ra, rb, mp.unhex(r['proof']))[0] == mp.OK
+    for r in fx['neg_consistency']:
+        if mp.negative(r):
+            continue
+        got = md.ref_consistency(*_cons_args(r))
+        want = mp.expect_consistency(r)
+        assert all(w is None or w == g for w, g in zip(want, got)), r['what']
+        assert got == host_consistency(lib, *_cons_args(r)), r['what']
+
+
+def test_request_builders_weave_valid_and_refused(tree):
+    """tests/_merkle_device.py path_requests / proof_requests: alternating, the
+    edges and the 64-bit traps present, valid exactly where LevelTree accepts"""
+    import _merkle_device as md
+    n = 1000
+    for k in (1, 63, 64, 65, 257, 1000):
+        for phase in (0, 1):
+            for reqs, ok in ((md.path_requests(n, k, phase), lambda a, b: 0 <= a < b <= n),
+                             (md.proof_requests(n, k, phase), lambda a, b: 0 <= a <= b <= n)):
+                assert len(reqs) == k
+                assert [v for _, _, v in reqs] == [(i + phase) % 2 == 0 for i in range(k)]
+                assert all(ok(a, b) == v for a, b, v in reqs)
+                assert all(0 <= a < 2 ** 64 and 0 <= b < 2 ** 64 for a, b, _ in reqs)
+    paths = {(a, b) for a, b, v in md.path_requests(n, 1000, 0) if v}
+    assert {(0, 1), (0, n), (n - 1, n), (511, 512), (512, 513), (0, 513), (255, 511)} <= paths
+    assert len(paths - set(md.path_edges(n))) >= 64
+    proofs = {(a, b) for a, b, v in md.proof_requests(n, 1000, 0) if v}
+    assert {(0, 0), (0, n), (n, n), (1, 1), (511, 512), (513, n), (512, 513), (255, 257)} <= proofs
+    assert len(proofs - set(md.proof_edges(n))) >= 64
+    # every trap is out of range as 64 bits and in range once truncated to 32
+    low = 2 ** 32 - 1
+    assert sum(1 for a, b in md.path_refusals(n) if 0 <= (a & low) < (b & low) <= n) >= 4
+    assert sum(1 for a, b in md.proof_refusals(n) if 0 <= (a & low) <= (b & low) <= n) >= 4
+    assert {(2 ** 64 - 1, n), (0, 2 ** 63)} <= set(md.path_refusals(n))
+    assert all(x[0] < 2 ** 64 and x[1] < 2 ** 64 for x in md.path_refusals(n) + md.proof_refusals(n))
+
+
+def test_second_trip_class_tables(lib, fx):
+    """the class tables the GPU test repeats past one grid of the proof kernels
+    (tests/_merkle_device.py) against the fixture, LevelTree's RFC 6962
+    recursions and the header's routines on the host"""
+    import _merkle_device as md
+    lh = [bytes.fromhex(h) for h in mk.fixture()['leaf_hashes']]
+    t5 = md.small_tree(lh)
+    n = t5.size
+    assert n == 5 and len(t5.lv) - 1 == 3
+    for s in range(1, n + 1):
+        assert t5.root(s).hex() == fx['roots'][str(s)]
+    fx_paths = {(r['m'], r['s']): r['path'] for r in fx['audit_paths']}
+    fx_proofs = {(r['a'], r['b']): r['proof'] for r in fx['consistency']}
+    ht = lib.mc_tree_new(b''.join(t5.lv[0]), n)
+    try:
+        assert lib.mc_tree_depth(ht) == 3
+        out, root = np.zeros((4, 32), np.uint8), np.zeros(32, np.uint8)
+        pc = md.path_classes(t5)
+        assert len(pc) == 18 and sum(p is None for _, _, p, _ in pc) == 3
+        for m, s, path, rt in pc:
+            got = lib.mc_audit_path(ht, m, s, out.ctypes.data, root.ctypes.data)
+            if path is None:
+                assert got == md.REFUSED and rt is None and not (0 <= m < s <= n)
+                continue
+            assert got == len(path) <= 3 and out[:got].tobytes() == b''.join(path) and root.tobytes() == rt
+            assert path == mp.rfc_path(m, lh[:s]) and rt == mp.rfc_mth(lh[:s])
+            if (m, s) in fx_paths:
+                assert [h.hex() for h in path] == fx_paths[(m, s)]
+        assert {(m, s) for m, s, p, _ in pc if p is not None} == {(m, s) for s in range(1, 6) for m in range(s)}
+        cc = md.proof_classes(t5)
+        assert len(cc) == 23 and sum(p is None for _, _, p in cc) == 2
+        for a, b, proof in cc:
+            got = lib.mc_cons_proof(ht, a, b, out.ctypes.data)
+            if proof is None:
+                assert got == md.REFUSED and not (0 <= a <= b <= n)
+                continue
+            assert got == len(proof) <= 4 and out[:got].tobytes() == b''.join(proof)
+            if a >= 1:
+                assert proof == mp.rfc_proof(a, lh[:b])
+            if (a, b) in fx_proofs:
+                assert [h.hex() for h in proof] == fx_proofs[(a, b)]
+    finally:
+        lib.mc_tree_free(ht)
+    ic = md.incl_classes(t5)
+    assert [w[0] for _, w in ic] == [mp.OK] * 15 + [mp.ROOT_MISMATCH, mp.TOO_SHORT, mp.TOO_LONG, mp.BAD_RANGE]
+    for it, want in ic:
+        assert host_inclusion(lib, *it) == want, it[1:3]
+        if want[0] == mp.OK:
+            assert want[1] == t5.root(it[2]) == it[4]
+    assert ic[16][1][2] == 1 and ic[15][1][1] == t5.root(n)     # stopped at node 1; the true root computed
+    cc = md.cons_classes(t5)
+    assert [w[0] for _, w in cc] == [mp.OK] * 21 + [mp.ROOT_MISMATCH, mp.TOO_SHORT, mp.BAD_RANGE, mp.INCONSISTENT]
+    for it, want in cc:
+        assert host_consistency(lib, *it) == want, it[:2]
+    assert cc[24][1][2] == t5.root(n) and cc[24][1][1] == t5.root(3) != cc[24][0][2]
+
+
 def test_header_self_check_under_sanitizers():
     """tools/hostcheck/merklecheck_main.cpp: its own process, built with
     AddressSanitizer + UBSan; every path and proof of trees of 1..130 leaves
