@@ -246,46 +246,251 @@ PV_HD bool fits132(const uint32_t* v, int nw) {
   return (uint64_t)v[4] + 8u + c < 16u;
 }
 
-// h (< L, 8 words) -> |c|, d (HS_WORDS words each) with c == d h (mod 8L),
-// d odd and positive, |c|, d within the 132-bit windows; c_neg = sign of c.
-// Returns HS_HALF, or HS_DEFER when no such pair was found (see header).
-PV_HD uint32_t half_scalars(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, const uint32_t h[8]) {
-  uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
+// (ra, ta) <-> (rb, tb)
+PV_HD void hs_swap(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], uint32_t tb[HS_T]) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    ra[k] = sc_8L(k);
-    rb[k] = h[k];
+    const uint32_t x = ra[k];
+    ra[k] = rb[k];
+    rb[k] = x;
   }
 #pragma unroll
-  for (int k = 0; k < HS_T; ++k) ta[k] = tb[k] = 0;
-  tb[0] = 1;
-  // a_{i-1} = (ra, ta), a_i = (rb, tb); odd = parity of i.  Two steps per trip
-  // so the roles alternate without swapping registers; the exit swaps once.
-  uint32_t odd = 1;
+  for (int k = 0; k < HS_T; ++k) {
+    const uint32_t x = ta[k];
+    ta[k] = tb[k];
+    tb[k] = x;
+  }
+}
+
+// Euclid on a_{i-1} = (ra, ta), a_i = (rb, tb) down to the first r_i < 2^128,
+// one exact full-width step at a time; odd = parity of i.  Two steps per trip
+// so the roles alternate without swapping registers; the exit swaps once.
+// false: deferred (a quotient too large for one step, or more than 192 steps).
+PV_HD bool hs_euclid_classic(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], uint32_t tb[HS_T], uint32_t& odd) {
   int trips = 0;
 #pragma unroll 1
   for (;;) {
     if (!ge2_128(rb)) break;
-    if (++trips > 96 || !euclid_step(ra, ta, rb, tb)) return HS_DEFER;  // ra <- r_{i+1}
+    if (++trips > 96 || !euclid_step(ra, ta, rb, tb)) return false;  // ra <- r_{i+1}
     odd ^= 1u;
     if (!ge2_128(ra)) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const uint32_t x = ra[k];
-        ra[k] = rb[k];
-        rb[k] = x;
-      }
-#pragma unroll
-      for (int k = 0; k < HS_T; ++k) {
-        const uint32_t x = ta[k];
-        ta[k] = tb[k];
-        tb[k] = x;
-      }
+      hs_swap(ra, ta, rb, tb);
       break;
     }
-    if (!euclid_step(rb, tb, ra, ta)) return HS_DEFER;                   // rb <- r_{i+1}
+    if (!euclid_step(rb, tb, ra, ta)) return false;                   // rb <- r_{i+1}
     odd ^= 1u;
   }
+  return true;
+}
+
+// ---- the same reduction by Lehmer rounds (PV_LATTICE_LEHMER, default 1) ----
+// A round runs Euclid on the leading 53 bits of (ra, rb) only, collects the
+// quotients it can PROVE equal to the full-width ones in a 2x2 cofactor matrix
+// of magnitudes below 2^27, and applies the matrix to the long operands once.  The
+// partial quotients, the exit (first r_i < 2^128, always reached by an exact
+// full-width step) and hence every output word are those of hs_euclid_classic;
+// -DPV_LATTICE_LEHMER=0 builds the classical loop for A/B timing.
+//
+// With ra = xa 2^s + ea, rb = xb 2^s + eb (0 <= ea, eb < 2^s) and the cofactor
+// magnitudes u_j, v_j (u_{-1} = 1, v_{-1} = 0, u_0 = 0, v_0 = 1,
+// w_{j+1} = w_{j-1} + q_j w_j), r_j = (-1)^(j+1) (u_j ra - v_j rb), so the
+// leading-word remainder x_j = (-1)^(j+1) (u_j xa - v_j xb) brackets the true
+// one: r_j / 2^s lies in (x_j - v_j, x_j + v_j) (u_j <= v_j for j >= 0).  The
+// quotient q = floor(x_{j-1} / x_j) is the full-width one iff 0 <= r_{j+1} <
+// r_j, which follows from (Jebelean's condition, with v for both cofactors)
+//     x_{j+1} >= v_{j+1}   and   x_j - x_{j+1} >= v_{j+1} + v_j.
+// The first is strengthened to x_{j+1} >= v_{j+1} + T, T = ceil(2^128 / 2^s),
+// which proves r_{j+1} >= 2^128: a round never steps to or past the exit.
+#ifndef PV_LATTICE_LEHMER
+#define PV_LATTICE_LEHMER 1
+#endif
+constexpr int HS_MAX_STEPS = 192;   // the classical loop's 96 trips of two steps
+constexpr double HS_COF_CAP = 134217728.0;   // cofactors below 2^27: half the 53-bit window and a bit
+constexpr int HS_MAX_INNER = 48;    // v_j >= Fibonacci(j + 1), which passes 2^27 at j = 40
+constexpr double HS_QSCALE = 1.0 - 0x1p-44;
+
+// host-side statistics of one reduction (tools/hostcheck; never passed on the device)
+struct HsStats {
+  uint32_t rounds, inner, fallback, zero_rounds, exit_in_fallback;
+  uint8_t k[HS_MAX_STEPS + 1];   // proven steps of each round, in order (0: a fallback step)
+};
+
+// out = A x - B y (SUB) or A x + B y over N words, mod 2^(32 N); the callers'
+// exact results are non-negative and fit
+template <int N, bool SUB>
+PV_HD void lincomb(uint32_t out[N], uint32_t A, const uint32_t x[N], uint32_t B, const uint32_t y[N]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // independent products; low and (shifted) high words joined by one carry
+  // chain per product, the two sums by a third
+  uint32_t pl[N], ph[N], ml[N], mh[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint64_t p = (uint64_t)A * x[k], m = (uint64_t)B * y[k];
+    pl[k] = (uint32_t)p;
+    ph[k] = (uint32_t)(p >> 32);
+    ml[k] = (uint32_t)m;
+    mh[k] = (uint32_t)(m >> 32);
+  }
+  unsigned c1 = 0, c2 = 0, c3 = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint32_t p = __builtin_addc(pl[k], k ? ph[k - 1] : 0u, c1, &c1);
+    const uint32_t m = __builtin_addc(ml[k], k ? mh[k - 1] : 0u, c2, &c2);
+    out[k] = SUB ? __builtin_subc(p, m, c3, &c3) : __builtin_addc(p, m, c3, &c3);
+  }
+#else
+  uint64_t cp = 0, cm = 0, c = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint64_t p = (uint64_t)A * x[k] + cp, m = (uint64_t)B * y[k] + cm;
+    cp = p >> 32;
+    cm = m >> 32;
+    if (SUB) {
+      const uint64_t d = (uint64_t)(uint32_t)p - (uint32_t)m - c;
+      out[k] = (uint32_t)d;
+      c = d >> 63;
+    } else {
+      const uint64_t s = (uint64_t)(uint32_t)p + (uint32_t)m + c;
+      out[k] = (uint32_t)s;
+      c = s >> 32;
+    }
+  }
+#endif
+}
+
+// (hi:lo) << z, upper word; 0 <= z < 32
+PV_HD uint32_t shl_hi(uint32_t hi, uint32_t lo, uint32_t z) { return z ? (hi << z) | (lo >> (32u - z)) : hi; }
+
+// floor(x / y) within one from below, for integer-valued x >= y > 0 below 2^53:
+// the float64 estimate (relative error < 2^-48 either way) is scaled by
+// 1 - 2^-44, so while the quotient is below 2^27 it is q or q - 1, never above
+PV_HD double quot53_est(double x, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r = __builtin_amdgcn_rcp(y);
+  r = fma(r, fma(-y, r, 1.0), r);
+  r = fma(r, fma(-y, r, 1.0), r);
+  return floor(x * r * HS_QSCALE);
+#else
+  return floor(x / y * HS_QSCALE);
+#endif
+}
+
+// One round on the leading 53 bits of ra > rb >= 2^128: the number k of proven
+// steps (0: none) and their matrix (u0, v0, u1, v1) = (u_{k-1}, v_{k-1}, u_k,
+// v_k).  -1: the inner loop overran its bound (cannot happen; deferred).
+// The window, the remainders and the cofactors are integers below 2^53 held in
+// float64, where every product, sum and difference below is exact: the GPU has
+// no 64-bit divide, and its float64 rate is that of its 32-bit integer adds.
+PV_HD int lehmer_round(const uint32_t ra[8], const uint32_t rb[8], uint32_t& u0, uint32_t& v0, uint32_t& u1,
+                       uint32_t& v1) {
+  // the three leading words of ra (top one non-zero, word index w >= 4) and rb's
+  // at the same place, by selects: no indexed access to the register arrays
+  uint32_t a2 = ra[7], a1 = ra[6], a0 = ra[5], b2 = rb[7], b1 = rb[6], b0 = rb[5];
+  uint32_t w = 7;
+#pragma unroll
+  for (int k = 4; k >= 2; --k) {
+    if (a2 == 0) {
+      a2 = a1; a1 = a0; a0 = ra[k];
+      b2 = b1; b1 = b0; b0 = rb[k];
+      --w;
+    }
+  }
+  u0 = 1; v0 = 0; u1 = 0; v1 = 1;
+  if (a2 == 0) return 0;               // ra < 2^128: outside the loop's invariant
+  const uint32_t z = (uint32_t)__builtin_clz(a2);
+  // the leading 64 bits (shift counts 1..31 only), then their upper 53:
+  // s = 32 (w - 1) - z + 11 and T = 2^(128 - s), or 1 once s >= 128
+  const uint64_t x64 = ((uint64_t)shl_hi(a2, a1, z) << 32) | shl_hi(a1, a0, z);
+  const uint64_t y64 = ((uint64_t)shl_hi(b2, b1, z) << 32) | shl_hi(b1, b0, z);
+  const uint64_t T64 = w == 4 ? (uint64_t)(1u << z) << 32 : (w == 5 ? (uint64_t)(1u << z) : 1u);
+  double x = (double)(x64 >> 11), y = (double)(y64 >> 11);
+  const double T = (T64 >> 11) ? (double)(T64 >> 11) : 1.0;
+  if (!(y > 0.0) || x < y) return 0;
+  double du0 = 1.0, dv0 = 0.0, du1 = 0.0, dv1 = 1.0;
+  int k = 0;
+#pragma unroll 1
+  for (; k < HS_MAX_INNER; ++k) {
+    double q = quot53_est(x, y);
+    double rem = x - q * y;                          // q y <= x: exact
+    const bool up = rem >= y;
+    rem -= up ? y : 0.0;
+    q += up ? 1.0 : 0.0;
+    const double nv = q * dv1 + dv0;                 // exact below the cap; above it, above it
+    // cofactor cap (and with it q < 2^27, where the estimate holds);
+    // r_{j+1} >= 2^128 proven; r_{j+1} < r_j proven
+    if (!(nv < HS_COF_CAP && rem >= nv + T && y - rem >= nv + dv1)) break;
+    const double nu = q * du1 + du0;
+    x = y; y = rem;
+    du0 = du1; du1 = nu;
+    dv0 = dv1; dv1 = nv;
+  }
+  u0 = (uint32_t)du0; v0 = (uint32_t)dv0; u1 = (uint32_t)du1; v1 = (uint32_t)dv1;
+  return k < HS_MAX_INNER ? k : -1;
+}
+
+PV_HD bool hs_euclid_lehmer(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], uint32_t tb[HS_T], uint32_t& odd,
+                            HsStats* stats = nullptr) {
+  // a_{i-1} = (ra, ta), a_i = (rb, tb) at the top of every trip; every trip
+  // takes at least one step, so HS_MAX_STEPS + 1 trips bound the loop
+  int steps = 0;
+#pragma unroll 1
+  for (int trip = 0; trip <= HS_MAX_STEPS; ++trip) {
+    if (!ge2_128(rb)) return true;
+    if (steps >= HS_MAX_STEPS) return false;         // the classical loop's trips > 96
+    uint32_t u0, v0, u1, v1;
+    const int k = lehmer_round(ra, rb, u0, v0, u1, v1);
+    if (k < 0) return false;
+    if (stats) {
+      stats->k[stats->rounds] = (uint8_t)k;
+      ++stats->rounds;
+      stats->inner += (uint32_t)k;
+      stats->zero_rounds += k == 0;
+    }
+    if (k == 0) {
+      // nothing proven (a large quotient, leading words too close, or the exit
+      // within reach): one exact full-width step, as the classical loop takes it
+      if (!euclid_step(ra, ta, rb, tb)) return false;
+      hs_swap(ra, ta, rb, tb);
+      steps += 1;
+      odd ^= 1u;
+      if (stats) {
+        ++stats->fallback;
+        stats->exit_in_fallback += !ge2_128(rb);
+      }
+      continue;
+    }
+    // k even: (r_{k-1}, r_k) = (u0 ra - v0 rb, v1 rb - u1 ra); k odd: the
+    // negatives.  |t_{k-1}|, |t_k| = u0 ta + v0 tb, u1 ta + v1 tb either way.
+    uint32_t na[8], nb[8], sa[HS_T], sb[HS_T];
+    if (k & 1) {
+      lincomb<8, true>(na, v0, rb, u0, ra);
+      lincomb<8, true>(nb, u1, ra, v1, rb);
+    } else {
+      lincomb<8, true>(na, u0, ra, v0, rb);
+      lincomb<8, true>(nb, v1, rb, u1, ra);
+    }
+    lincomb<HS_T, false>(sa, u0, ta, v0, tb);
+    lincomb<HS_T, false>(sb, u1, ta, v1, tb);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      ra[j] = na[j];
+      rb[j] = nb[j];
+    }
+#pragma unroll
+    for (int j = 0; j < HS_T; ++j) {
+      ta[j] = sa[j];
+      tb[j] = sb[j];
+    }
+    steps += k;
+    odd ^= (uint32_t)k & 1u;
+  }
+  return false;                                       // trip bound (cannot happen)
+}
+
+// The selection after the reduction: a_{i-1} = (ra, ta), a_i = (rb, tb) with
+// r_i the first remainder < 2^128, odd = parity of i.
+PV_HD uint32_t hs_select(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, uint32_t ra[8], uint32_t ta[HS_T],
+                         const uint32_t rb[8], const uint32_t tb[HS_T], uint32_t odd) {
   if (tb[0] & 1u) {
     // a_i itself: r_i < 2^128, |t_i| < 2^128; t_i < 0 iff i even
     c_neg = odd == 0;
@@ -322,6 +527,53 @@ PV_HD uint32_t half_scalars(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_
   }
   return HS_HALF;
 }
+
+PV_HD void hs_init(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], uint32_t tb[HS_T], const uint32_t h[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    ra[k] = sc_8L(k);
+    rb[k] = h[k];
+  }
+#pragma unroll
+  for (int k = 0; k < HS_T; ++k) ta[k] = tb[k] = 0;
+  tb[0] = 1;
+}
+
+// h (< L, 8 words) -> |c|, d (HS_WORDS words each) with c == d h (mod 8L),
+// d odd and positive, |c|, d within the 132-bit windows; c_neg = sign of c.
+// Returns HS_HALF, or HS_DEFER when no such pair was found (see header).
+PV_HD uint32_t half_scalars(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, const uint32_t h[8]) {
+  uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
+  hs_init(ra, ta, rb, tb, h);
+  uint32_t odd = 1;
+#if PV_LATTICE_LEHMER
+  if (!hs_euclid_lehmer(ra, ta, rb, tb, odd)) return HS_DEFER;
+#else
+  if (!hs_euclid_classic(ra, ta, rb, tb, odd)) return HS_DEFER;
+#endif
+  return hs_select(c, d, c_neg, ra, ta, rb, tb, odd);
+}
+
+#if !defined(__HIPCC__)
+// host builds only: the classical loop whatever the switch says (the tests'
+// reference), and the Lehmer rounds with their statistics
+inline uint32_t half_scalars_classic(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, const uint32_t h[8]) {
+  uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
+  hs_init(ra, ta, rb, tb, h);
+  uint32_t odd = 1;
+  if (!hs_euclid_classic(ra, ta, rb, tb, odd)) return HS_DEFER;
+  return hs_select(c, d, c_neg, ra, ta, rb, tb, odd);
+}
+
+inline uint32_t half_scalars_lehmer(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, const uint32_t h[8],
+                                    HsStats* stats) {
+  uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
+  hs_init(ra, ta, rb, tb, h);
+  uint32_t odd = 1;
+  if (!hs_euclid_lehmer(ra, ta, rb, tb, odd, stats)) return HS_DEFER;
+  return hs_select(c, d, c_neg, ra, ta, rb, tb, odd);
+}
+#endif
 
 // v + 0x88..8 (33 nibbles), in place: the offset form whose nibble w minus 8
 // is signed digit w (callers guarantee fits132)

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Interleaved A/B/... of several builds of libplenum_verify.so on one box:
 #   bash tools/ab_libs.sh OUT ROUNDS "LIB1 LIB2 ..." [bench args...]
-# one JSON line per run in OUT/ab.jsonl, tagged with the library.
+# one JSON line per run in OUT/ab.jsonl, tagged with the library; the runs' whole
+# result lines (stages, kernel_ms, latencies) are kept in OUT/runs.jsonl.
 set -u
 out=$1; rounds=$2; libs=$3; shift 3
 mkdir -p "$out"
@@ -11,6 +12,8 @@ for r in $(seq 1 "$rounds"); do
     python - "$lib" "$out/run.json" "$*" >> "$out/ab.jsonl" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
+with open(sys.argv[2].rsplit('/', 1)[0] + '/runs.jsonl', 'a') as fh:
+    fh.write(json.dumps({'lib': sys.argv[1], 'args': sys.argv[3], 'result': d}) + '\n')
 print(json.dumps({'lib': sys.argv[1], 'args': sys.argv[3], 'value': d['value'], 'ms_per_step': d['ms_per_step'],
                   'frac': (d.get('roofline') or {}).get('frac')}))
 PY

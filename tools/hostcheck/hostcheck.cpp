@@ -242,6 +242,51 @@ uint32_t hc_half_scalars(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_
   return st;
 }
 
+// the same through the classical one-step-at-a-time loop (the reference of the
+// Lehmer rounds, whatever PV_LATTICE_LEHMER says)
+uint32_t hc_half_scalars_classic(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_t* c_neg) {
+  uint32_t h[8], c[HS_WORDS], d[HS_WORDS];
+  memcpy(h, h32, 32);
+  bool neg = false;
+  const uint32_t st = half_scalars_classic(c, d, neg, h);
+  memcpy(c20, c, 4 * HS_WORDS);
+  memcpy(d20, d, 4 * HS_WORDS);
+  *c_neg = neg ? 1u : 0u;
+  return st;
+}
+
+// the same through the Lehmer rounds, whatever PV_LATTICE_LEHMER says
+uint32_t hc_half_scalars_lehmer(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_t* c_neg) {
+  uint32_t h[8], c[HS_WORDS], d[HS_WORDS];
+  memcpy(h, h32, 32);
+  bool neg = false;
+  const uint32_t st = half_scalars_lehmer(c, d, neg, h, nullptr);
+  memcpy(c20, c, 4 * HS_WORDS);
+  memcpy(d20, d, 4 * HS_WORDS);
+  *c_neg = neg ? 1u : 0u;
+  return st;
+}
+
+// the Lehmer rounds of one h: stats5 = rounds, inner (leading-word) steps,
+// full-width fallback steps, rounds that proved no step, fallback steps that
+// reached the exit; ks (may be NULL, 193 bytes) = the proven steps of each
+// round in order, 0 for a fallback step; returns half_scalars' status
+uint32_t hc_lattice_rounds(const uint8_t* h32, uint32_t* stats5, uint8_t* ks) {
+  uint32_t h[8], c[HS_WORDS], d[HS_WORDS];
+  memcpy(h, h32, 32);
+  bool neg = false;
+  HsStats s;
+  memset(&s, 0, sizeof s);
+  const uint32_t st = half_scalars_lehmer(c, d, neg, h, &s);
+  stats5[0] = s.rounds;
+  stats5[1] = s.inner;
+  stats5[2] = s.fallback;
+  stats5[3] = s.zero_rounds;
+  stats5[4] = s.exit_in_fallback;
+  if (ks) memcpy(ks, s.k, sizeof s.k);
+  return st;
+}
+
 // s' = d * S mod L (d: 20 LE bytes, S: 32 LE bytes)
 void hc_sc_mul_small(const uint8_t* d20, const uint8_t* s32, uint8_t* out32) {
   uint32_t d[HS_WORDS], S[8], r[8];
