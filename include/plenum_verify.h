@@ -323,6 +323,58 @@ int pv_merkle_consistency_proofs(int32_t handle, const uint64_t *first, const ui
 int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t *first, const uint64_t *second, uint64_t k,
                                         uint8_t *nodes_out, uint32_t *len_out, void *stream);
 
+/* The ledger write cycle on the resident tree: with these a ledger needs no host-side
+ * CompactMerkleTree.  A tree holds `committed` <= n leaves; leaves [committed, n) are staged.
+ * pv_merkle_tree_extend* appends and commits as before and is PV_EINVAL while leaves are staged;
+ * pv_merkle_tree_info and the proof calls keep reading all n leaves (the committed view is
+ * tree_size <= committed).  Every call is synchronous and ordered on the tree's stream.
+ *   pv_merkle_tree_stage / _stage_hashes / _stage_hashes_device
+ *       append k staged leaves (HOST blob / off; k x 32 leaf hashes in HOST / DEVICE memory);
+ *       root_out (HOST, may be NULL) = MTH(0, n) afterwards: Ledger.appendTxns ->
+ *       uncommittedRootHash, treeWithAppliedTxns (plenum/common/ledger.py:38-57, 129-143).
+ *       k <= 1024 rebuilds the right edge in one launch of one workgroup.  k == 0 is PV_OK and
+ *       writes nothing, root_out included (pv_merkle_tree_discard(handle, 0, root) reads the root).
+ *   pv_merkle_tree_commit        committed += count, no device work: Ledger.commitTxns
+ *                                (plenum/common/ledger.py:75-100); count > n - committed is PV_EINVAL
+ *   pv_merkle_tree_discard       drop the last `count` staged leaves and repair the right edge in
+ *                                one launch: Ledger.discardTxns / reset_uncommitted
+ *                                (plenum/common/ledger.py:102-148).  root_out (may be NULL) = the
+ *                                new root, SHA-256("") for an empty tree.  count > n - committed is
+ *                                PV_EINVAL (the reference's LogicError) and changes nothing.
+ *   pv_merkle_tree_sizes         *committed and *total (= n)
+ *   pv_merkle_tree_frontier      CompactMerkleTree.hashes (ledger/compact_merkle_tree.py:77-79, what
+ *                                save / load / __copy__ carry, :47-63) of the prefix of tree_size <= n
+ *                                leaves: *count_out = popcount(tree_size) full-subtree roots, largest
+ *                                first, in hashes_out (room for 64 x 32 bytes; NULL: the count only)
+ *   pv_merkle_tree_hash_store[_device]
+ *       what the hash store receives while leaves first + 1 .. last (sequence numbers, last <= n)
+ *       are appended one by one (CompactMerkleTree._push_subtree, ledger/compact_merkle_tree.py:
+ *       95-136; HashStore.writeLeaf / writeNode): leaf_out = their (last - first) leaf hashes,
+ *       node_out = the completed nodes in writeNode order, *n_nodes = (last - popcount(last)) -
+ *       (first - popcount(first)) of them.  Leaf e completes ctz(e) nodes, height h = 1 .. ctz(e),
+ *       1-based store position (e - 1) - popcount(e - 1) + h (HashStore.getNodePosition(e, h)).
+ *       Either output may be NULL.  node_cap < *n_nodes is PV_EINVAL with the need in *n_nodes and
+ *       nothing written.  The _device form writes DEVICE buffers (16-byte aligned) on `stream`.
+ *   pv_merkle_tree_check_nodes   the same range and order compared with node_hashes (HOST):
+ *                                *n_bad = differing nodes, *first_bad = the smallest differing index
+ *                                or UINT64_MAX.  The content check that
+ *                                Ledger.recoverTreeFromHashStore / CompactMerkleTree.verify_consistency
+ *                                (ledger/compact_merkle_tree.py:280-289: counts only) lack. */
+int pv_merkle_tree_stage(int32_t handle, const uint8_t *blob, const uint64_t *off, uint64_t k, uint8_t *root_out);
+int pv_merkle_tree_stage_hashes(int32_t handle, const uint8_t *leaf_hashes, uint64_t k, uint8_t *root_out);
+int pv_merkle_tree_stage_hashes_device(int32_t handle, const uint8_t *leaf_hashes, uint64_t k, uint8_t *root_out,
+                                       void *stream);
+int pv_merkle_tree_commit(int32_t handle, uint64_t count);
+int pv_merkle_tree_discard(int32_t handle, uint64_t count, uint8_t *root_out);
+int pv_merkle_tree_sizes(int32_t handle, uint64_t *committed, uint64_t *total);
+int pv_merkle_tree_frontier(int32_t handle, uint64_t tree_size, uint8_t *hashes_out, uint32_t *count_out);
+int pv_merkle_tree_hash_store(int32_t handle, uint64_t first, uint64_t last, uint8_t *leaf_out, uint8_t *node_out,
+                              uint64_t node_cap, uint64_t *n_nodes);
+int pv_merkle_tree_hash_store_device(int32_t handle, uint64_t first, uint64_t last, uint8_t *leaf_out,
+                                     uint8_t *node_out, uint64_t node_cap, uint64_t *n_nodes, void *stream);
+int pv_merkle_tree_check_nodes(int32_t handle, uint64_t first, uint64_t last, const uint8_t *node_hashes,
+                               uint64_t *n_bad, uint64_t *first_bad);
+
 /* SHA3-256 and Patricia-trie state proofs, batched: the third check of a read reply
  * (plenum/server/request_handlers/handler_interfaces/read_request_handler.py:39-59).
  *   pv_sha3_256_batch[_device]

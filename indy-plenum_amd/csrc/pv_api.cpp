@@ -2217,6 +2217,7 @@ struct MerkleTree {
   bool live = false;
   int dev = -1;           // Device::id
   uint64_t n = 0;         // leaves
+  uint64_t committed = 0; // leaves [committed, n) are staged (pv_merkle_tree_stage*)
   uint32_t depth = 0;     // levels above the leaves
   uint64_t hint = 1;
   std::vector<uint32_t*> lv;
@@ -2310,6 +2311,52 @@ int tree_rebuild(MerkleTree& t, uint64_t n_new, hipStream_t s) {
     t.dirty = false;
   }
   return PV_OK;
+}
+
+// extend* appends and commits: refused while leaves are staged
+int tree_unstaged(const MerkleTree& t) {
+  if (t.committed == t.n) return PV_OK;
+  return fail(PV_EINVAL, "the tree holds %llu staged leaves: commit or discard them before extend",
+              (unsigned long long)(t.n - t.committed));
+}
+
+// the tree has n_new leaves and the leaves from f0 on are new (stage: f0 = the old size) or lost
+// their right neighbours (discard: f0 = n_new - 1): one k_merkle_edge launch rebuilds their ancestors
+int tree_edge(MerkleTree& t, uint64_t f0, uint64_t n_new, hipStream_t s) {
+  uint32_t depth = 0;
+  for (uint64_t m = n_new; m > 1; m = (m + 1) / 2) {
+    ++depth;
+    if (const int rc = tree_grow(t, depth, (m + 1) / 2, s)) return rc;
+  }
+  if (n_new > 1) HIP_OK(pv::launch_merkle_edge(t.lv.data(), depth + 1, f0, n_new, s));
+  t.depth = depth;
+  t.n = n_new;
+  if (t.dirty) {   // a level moved: the table the read kernels use, as tree_rebuild uploads it
+    t.host_table.assign(MT_LEVELS, nullptr);
+    for (size_t i = 0; i < t.lv.size(); ++i) t.host_table[i] = t.lv[i];
+    HIP_OK(hipMemcpyAsync(t.table, t.host_table.data(), MT_LEVELS * sizeof(uint32_t*), hipMemcpyHostToDevice, s));
+    t.dirty = false;
+  }
+  return PV_OK;
+}
+
+// root (HOST, may be null) <- MTH(0, n) once the work queued on s is done
+int tree_root(const MerkleTree& t, uint8_t* root, hipStream_t s) {
+  if (!root) return PV_OK;
+  if (t.n == 0) {
+    memcpy(root, EMPTY_ROOT, 32);
+    return PV_OK;
+  }
+  HIP_OK(hipMemcpyAsync(root, t.lv[t.depth], 32, hipMemcpyDeviceToHost, s));
+  return PV_OK;
+}
+
+// k staged leaf hashes are in level 0 behind the n the tree has: their ancestors.  Up to
+// MERKLE_EDGE_MAX leaves in one launch, more by the per-level rebuild of extend.
+int tree_stage(MerkleTree& t, uint64_t k, uint8_t* root_out, hipStream_t s) {
+  const int rc = k <= pv::MERKLE_EDGE_MAX ? tree_edge(t, t.n, t.n + k, s) : tree_rebuild(t, t.n + k, s);
+  if (rc) return rc;
+  return tree_root(t, root_out, s);
 }
 
 // resolve a handle to its tree and point the (host-form) entry scope at the
@@ -2534,10 +2581,13 @@ static int tree_extend_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64
   if (k == 0) return PV_OK;
   if (!leaf_hashes) return fail(PV_EINVAL, "null buffer");
   if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
+  if (const int rc = tree_unstaged(*t)) return rc;
   if (const int rc = en.begin(stream)) return rc;
   if (const int rc = tree_grow(*t, 0, t->n + k, en.s)) return rc;
   HIP_OK(hipMemcpyAsync(t->lv[0] + 8 * t->n, leaf_hashes, k * 32, kind, en.s));
-  return en.finish(tree_rebuild(*t, t->n + k, en.s));
+  if (const int rc = tree_rebuild(*t, t->n + k, en.s)) return rc;
+  t->committed = t->n;
+  return en.finish();
 }
 
 int pv_merkle_tree_extend_hashes_device(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, void* stream) {
@@ -2557,13 +2607,16 @@ int pv_merkle_tree_extend(int32_t handle, const uint8_t* blob, const uint64_t* o
   if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
   Ragged leaf(off, k);
   if (const int rc = leaf.check("off")) return rc;
+  if (const int rc = tree_unstaged(*t)) return rc;
   if (const int rc = en.begin()) return rc;
   Device* d = en.d;
   hipStream_t s = en.s;
   if (const int rc = leaf.stage(blob, *d, s)) return rc;
   if (const int rc = tree_grow(*t, 0, t->n + k, s)) return rc;
   HIP_OK(pv::launch_sha256(d->blob.p, d->off.p, k, 1, 0x00, d->counter.p, t->lv[0] + 8 * t->n, d->sha256_blocks, s));
-  return en.finish(tree_rebuild(*t, t->n + k, s));
+  if (const int rc = tree_rebuild(*t, t->n + k, s)) return rc;
+  t->committed = t->n;
+  return en.finish();
 }
 
 int pv_merkle_tree_info(int32_t handle, uint64_t* n, uint32_t* depth, uint8_t* root) {
@@ -2646,6 +2699,190 @@ int pv_merkle_consistency_proofs_device(int32_t handle, const uint64_t* first, c
 int pv_merkle_consistency_proofs(int32_t handle, const uint64_t* first, const uint64_t* second, uint64_t k,
                                  uint8_t* nodes_out, uint32_t* len_out) {
   return tree_requests(handle, first, second, k, nodes_out, len_out, nullptr, false, true, nullptr);
+}
+
+// ------------------------------------------------ the ledger write cycle
+// stage k leaf hashes from host or device memory
+static int tree_stage_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, uint8_t* root_out,
+                             hipMemcpyKind kind, void* stream) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (k == 0) return PV_OK;   // as extend: nothing staged, nothing written
+  if (!leaf_hashes) return fail(PV_EINVAL, "null buffer");
+  if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
+  if (const int rc = en.begin(stream)) return rc;
+  if (const int rc = tree_grow(*t, 0, t->n + k, en.s)) return rc;
+  HIP_OK(hipMemcpyAsync(t->lv[0] + 8 * t->n, leaf_hashes, k * 32, kind, en.s));
+  return en.finish(tree_stage(*t, k, root_out, en.s));
+}
+
+int pv_merkle_tree_stage_hashes(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, uint8_t* root_out) {
+  return tree_stage_hashes(handle, leaf_hashes, k, root_out, hipMemcpyHostToDevice, nullptr);
+}
+
+int pv_merkle_tree_stage_hashes_device(int32_t handle, const uint8_t* leaf_hashes, uint64_t k, uint8_t* root_out,
+                                       void* stream) {
+  return tree_stage_hashes(handle, leaf_hashes, k, root_out, hipMemcpyDeviceToDevice, stream);
+}
+
+int pv_merkle_tree_stage(int32_t handle, const uint8_t* blob, const uint64_t* off, uint64_t k, uint8_t* root_out) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (k == 0) return PV_OK;   // as extend: nothing staged, nothing written
+  if (!off || (!blob && off[k] != off[0])) return fail(PV_EINVAL, "null buffer");
+  if (k > (1ull << 40) || t->n + k > (1ull << 40)) return fail(PV_EINVAL, "tree limited to 2^40 leaves");
+  Ragged leaf(off, k);
+  if (const int rc = leaf.check("off")) return rc;
+  if (const int rc = en.begin()) return rc;
+  Device* d = en.d;
+  hipStream_t s = en.s;
+  if (const int rc = leaf.stage(blob, *d, s)) return rc;
+  if (const int rc = tree_grow(*t, 0, t->n + k, s)) return rc;
+  HIP_OK(pv::launch_sha256(d->blob.p, d->off.p, k, 1, 0x00, d->counter.p, t->lv[0] + 8 * t->n, d->sha256_blocks, s));
+  return en.finish(tree_stage(*t, k, root_out, s));
+}
+
+int pv_merkle_tree_commit(int32_t handle, uint64_t count) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (count > t->n - t->committed)
+    return fail(PV_EINVAL, "commit of %llu leaves, %llu staged", (unsigned long long)count,
+                (unsigned long long)(t->n - t->committed));
+  t->committed += count;
+  return PV_OK;
+}
+
+int pv_merkle_tree_discard(int32_t handle, uint64_t count, uint8_t* root_out) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (count > t->n - t->committed)
+    return fail(PV_EINVAL, "expected to revert %llu txns while there are only %llu", (unsigned long long)count,
+                (unsigned long long)(t->n - t->committed));
+  if (const int rc = en.begin()) return rc;
+  if (count) {
+    const uint64_t n_new = t->n - count;
+    if (const int rc = tree_edge(*t, n_new ? n_new - 1 : 0, n_new, en.s)) return rc;
+  }
+  return en.finish(tree_root(*t, root_out, en.s));
+}
+
+int pv_merkle_tree_sizes(int32_t handle, uint64_t* committed, uint64_t* total) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (committed) *committed = t->committed;
+  if (total) *total = t->n;
+  return PV_OK;
+}
+
+int pv_merkle_tree_frontier(int32_t handle, uint64_t tree_size, uint8_t* hashes_out, uint32_t* count_out) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (tree_size > t->n)
+    return fail(PV_EINVAL, "frontier of %llu leaves outside a tree of %llu", (unsigned long long)tree_size,
+                (unsigned long long)t->n);
+  const uint32_t cnt = (uint32_t)__builtin_popcountll(tree_size);
+  if (count_out) *count_out = cnt;
+  if (cnt == 0 || !hashes_out) return PV_OK;
+  if (const int rc = en.begin()) return rc;
+  TmpBuf<uint8_t> dout;
+  StreamDrain tail{en.s};
+  HIP_OK(dout.alloc(64 * 32));
+  HIP_OK(pv::launch_merkle_frontier(t->table, tree_size, w32(dout.p), en.s));
+  HIP_OK(hipMemcpyAsync(hashes_out, dout.p, (size_t)cnt * 32, hipMemcpyDeviceToHost, en.s));
+  return tail.finish();
+}
+
+// nodes the reference's hash store receives while leaves first + 1 .. last are appended
+static uint64_t hs_nodes(uint64_t first, uint64_t last) {
+  return (last - (uint64_t)__builtin_popcountll(last)) - (first - (uint64_t)__builtin_popcountll(first));
+}
+
+static int tree_hs_range(const MerkleTree& t, uint64_t first, uint64_t last) {
+  if (first > last || last > t.n)
+    return fail(PV_EINVAL, "leaves (%llu, %llu] outside a tree of %llu", (unsigned long long)first,
+                (unsigned long long)last, (unsigned long long)t.n);
+  return PV_OK;
+}
+
+static int tree_hash_store(int32_t handle, uint64_t first, uint64_t last, uint8_t* leaf_out, uint8_t* node_out,
+                           uint64_t node_cap, uint64_t* n_nodes, bool host, void* stream) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (const int rc = tree_hs_range(*t, first, last)) return rc;
+  const uint64_t need = hs_nodes(first, last);
+  if (n_nodes) *n_nodes = need;
+  if (node_out && node_cap < need)
+    return fail(PV_EINVAL, "node_cap %llu below the %llu nodes of the range", (unsigned long long)node_cap,
+                (unsigned long long)need);
+  if (first == last || (!leaf_out && !(node_out && need))) return PV_OK;
+  if (!host && (misaligned16(leaf_out) || misaligned16(node_out)))
+    return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> dleaf, dnode;
+  StreamDrain tail{s};
+  uint8_t *pl = leaf_out, *pn = need ? node_out : nullptr;
+  if (host) {
+    if (pl) {
+      HIP_OK(dleaf.alloc((last - first) * 32));
+      pl = dleaf.p;
+    }
+    if (pn) {
+      HIP_OK(dnode.alloc(need * 32));
+      pn = dnode.p;
+    }
+  }
+  HIP_OK(pv::launch_merkle_hs_gather(t->table, first, last, w32(pl), w32(pn), merkle_blocks(*en.d), s));
+  if (host) {
+    if (pl) HIP_OK(hipMemcpyAsync(leaf_out, pl, (last - first) * 32, hipMemcpyDeviceToHost, s));
+    if (pn) HIP_OK(hipMemcpyAsync(node_out, pn, need * 32, hipMemcpyDeviceToHost, s));
+  }
+  return tail.finish();
+}
+
+int pv_merkle_tree_hash_store(int32_t handle, uint64_t first, uint64_t last, uint8_t* leaf_out, uint8_t* node_out,
+                              uint64_t node_cap, uint64_t* n_nodes) {
+  return tree_hash_store(handle, first, last, leaf_out, node_out, node_cap, n_nodes, true, nullptr);
+}
+
+int pv_merkle_tree_hash_store_device(int32_t handle, uint64_t first, uint64_t last, uint8_t* leaf_out,
+                                     uint8_t* node_out, uint64_t node_cap, uint64_t* n_nodes, void* stream) {
+  return tree_hash_store(handle, first, last, leaf_out, node_out, node_cap, n_nodes, false, stream);
+}
+
+int pv_merkle_tree_check_nodes(int32_t handle, uint64_t first, uint64_t last, const uint8_t* node_hashes,
+                               uint64_t* n_bad, uint64_t* first_bad) {
+  Entry en;
+  MerkleTree* t;
+  if (const int rc = tree_enter(en, handle, &t)) return rc;
+  if (const int rc = tree_hs_range(*t, first, last)) return rc;
+  if (!n_bad || !first_bad) return fail(PV_EINVAL, "null pointer");
+  const uint64_t need = hs_nodes(first, last);
+  *n_bad = 0;
+  *first_bad = UINT64_MAX;
+  if (need == 0) return PV_OK;
+  if (!node_hashes) return fail(PV_EINVAL, "null buffer");
+  if (const int rc = en.begin()) return rc;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> dnodes;
+  TmpBuf<unsigned long long> dres;
+  StreamDrain tail{s};
+  unsigned long long res[2] = {0, ~0ull};
+  HIP_OK(dnodes.put(node_hashes, need * 32, s));
+  HIP_OK(dres.put(res, 2, s));
+  HIP_OK(pv::launch_merkle_hs_check(t->table, first, last, w32(dnodes.p), dres.p, merkle_blocks(*en.d), s));
+  HIP_OK(hipMemcpyAsync(res, dres.p, sizeof(res), hipMemcpyDeviceToHost, s));
+  if (const int rc = tail.finish()) return rc;
+  *n_bad = res[0];
+  *first_bad = res[1];
+  return PV_OK;
 }
 
 // ------------------------------------------------ SHA3-256 / state proofs

@@ -183,6 +183,21 @@ hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint
                                      const uint64_t* second, uint64_t k, uint32_t* nodes_out, uint32_t* len_out,
                                      int max_blocks, hipStream_t s);
 
+// The ledger write cycle over a resident tree (pv_merkle_ledger.h).
+//   edge       every ancestor of the leaves [f0, n_new), f0 < n_new <= f0 + MERKLE_EDGE_MAX, in one
+//              launch of one workgroup; levels[0 .. n_levels) are HOST-side copies of the level
+//              pointers, level l with room for the nodes of n_new leaves
+//   hs_gather  leaf hashes and writeNode-ordered nodes of the leaves (first, last]; either output may be null
+//   hs_check   the same nodes compared with `nodes`: res[0] += differing, res[1] = min(res[1], first differing)
+//   frontier   CompactMerkleTree.hashes of the prefix of `size` leaves, largest subtree first
+constexpr uint32_t MERKLE_EDGE_MAX = 1024;
+hipError_t launch_merkle_edge(uint32_t* const* levels, uint32_t n_levels, uint64_t f0, uint64_t n_new, hipStream_t s);
+hipError_t launch_merkle_hs_gather(const uint32_t* const* lv, uint64_t first, uint64_t last, uint32_t* leaf_out,
+                                   uint32_t* node_out, int max_blocks, hipStream_t s);
+hipError_t launch_merkle_hs_check(const uint32_t* const* lv, uint64_t first, uint64_t last, const uint32_t* nodes,
+                                  unsigned long long* res, int max_blocks, hipStream_t s);
+hipError_t launch_merkle_frontier(const uint32_t* const* lv, uint64_t size, uint32_t* out, hipStream_t s);
+
 // SHA3-256 / Patricia-trie state proofs (pv_sha3.h, pv_trie_proof.h).
 //   sha3_256     out (n x 8 words, 16-byte aligned) = SHA3-256(blob[beg[i] .. end[i])); the
 //                work queue of launch_sha256 (`counter` reset by the launch); the blob needs

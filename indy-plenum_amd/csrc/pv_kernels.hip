@@ -16,6 +16,7 @@
 #include "pv_quad.h"
 #include "pv_sha256.h"
 #include "pv_merkle_proof.h"
+#include "pv_merkle_ledger.h"
 #include "pv_sha3.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
@@ -1676,6 +1677,84 @@ hipError_t launch_merkle_cons_proofs(const uint32_t* const* lv, uint64_t n, uint
   if (k == 0) return hipSuccess;
   hipLaunchKernelGGL(k_merkle_cons_proofs, dim3(mp_grid(k, max_blocks)), dim3(256), 0, s, lv, n, depth, first, second,
                      k, nodes_out, len_out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------ ledger write cycle (pv_merkle_ledger.h)
+// Every ancestor of the leaves [f0, n_new) in ONE launch of one workgroup:
+// the changed nodes of a level go to the next through LDS (two buffers, one
+// barrier per level) and to the level buffers; the only global reads are the
+// leaf hashes and one untouched left sibling per level.  Stage (f0 = the old
+// size) and discard (f0 = n_new - 1) of a resident tree.
+static_assert(2 * ML_EDGE_BUF * 32 <= 40 * 1024, "k_merkle_edge: LDS of 2 x 513 nodes");
+__global__ __launch_bounds__(256) void k_merkle_edge(MlLevels lv, uint64_t f0, uint64_t n_new) {
+  __shared__ __attribute__((aligned(16))) uint32_t buf[2][ML_EDGE_BUF * 8];
+  ml_edge_rebuild(lv.lv, f0, n_new, buf[0], buf[1], threadIdx.x, 256u, [] { __syncthreads(); });
+}
+
+static_assert(MERKLE_EDGE_MAX == ML_EDGE_MAX, "the stage / discard span of one k_merkle_edge launch");
+hipError_t launch_merkle_edge(uint32_t* const* levels, uint32_t n_levels, uint64_t f0, uint64_t n_new, hipStream_t s) {
+  if (f0 >= n_new || n_new - f0 > (uint64_t)ML_EDGE_MAX || n_levels > ML_LEVELS) return hipErrorInvalidValue;
+  if (n_new == 1) return hipSuccess;
+  MlLevels lv{};
+  for (uint32_t l = 0; l < n_levels; ++l) lv.lv[l] = levels[l];
+  hipLaunchKernelGGL(k_merkle_edge, dim3(1), dim3(256), 0, s, lv, f0, n_new);
+  return hipGetLastError();
+}
+
+// one lane per leaf e of (first, last]: its hash and the ctz(e) nodes the
+// reference's hash store receives with it, in writeNode order
+__global__ __launch_bounds__(256) void k_merkle_hs_gather(const uint32_t* const* __restrict__ lv, uint64_t first,
+                                                          uint64_t last, uint32_t* __restrict__ leaf_out,
+                                                          uint32_t* __restrict__ node_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < last - first; i += stride)
+    ml_hs_gather(lv, first, first + 1 + i, leaf_out, node_out);
+}
+
+// the same walk comparing with `nodes`: res[0] += differing nodes, res[1] =
+// min(res[1], smallest differing index)
+__global__ __launch_bounds__(256) void k_merkle_hs_check(const uint32_t* const* __restrict__ lv, uint64_t first,
+                                                         uint64_t last, const uint32_t* __restrict__ nodes,
+                                                         unsigned long long* __restrict__ res) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < last - first; i += stride) {
+    uint64_t lowest = 0;
+    const uint32_t bad = ml_hs_check(lv, first, first + 1 + i, nodes, &lowest);
+    if (bad) {
+      atomicAdd(res, (unsigned long long)bad);
+      atomicMin(res + 1, (unsigned long long)lowest);
+    }
+  }
+}
+
+// CompactMerkleTree.hashes of the prefix of `size` leaves: one wave, lane b
+// gathers the node of bit b
+__global__ __launch_bounds__(64) void k_merkle_frontier(const uint32_t* const* __restrict__ lv, uint64_t size,
+                                                        uint32_t* __restrict__ out) {
+  const uint32_t b = threadIdx.x;
+  if ((size >> b) & 1) ml_frontier_node(lv, size, b, out);
+}
+
+hipError_t launch_merkle_hs_gather(const uint32_t* const* lv, uint64_t first, uint64_t last, uint32_t* leaf_out,
+                                   uint32_t* node_out, int max_blocks, hipStream_t s) {
+  if (first >= last) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_hs_gather, dim3(mp_grid(last - first, max_blocks)), dim3(256), 0, s, lv, first, last,
+                     leaf_out, node_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_hs_check(const uint32_t* const* lv, uint64_t first, uint64_t last, const uint32_t* nodes,
+                                  unsigned long long* res, int max_blocks, hipStream_t s) {
+  if (first >= last) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_hs_check, dim3(mp_grid(last - first, max_blocks)), dim3(256), 0, s, lv, first, last,
+                     nodes, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_frontier(const uint32_t* const* lv, uint64_t size, uint32_t* out, hipStream_t s) {
+  if (size == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_merkle_frontier, dim3(1), dim3(64), 0, s, lv, size, out);
   return hipGetLastError();
 }
 

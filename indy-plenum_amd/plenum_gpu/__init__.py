@@ -17,6 +17,9 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
   merkle          GpuTreeHasher, sha256_batch, merkle_root      ledger/tree_hasher.py
   merkle_proofs   GpuMerkleVerifier (+ *_batch), GpuMerkleTree
                   ledger/merkle_verifier.py, ledger/compact_merkle_tree.py
+  ledger_tree     GpuLedgerTree: the ledger's write cycle on the resident tree
+                  (appendTxns / commitTxns / discardTxns, hash store, catch-up)
+                  plenum/common/ledger.py, ledger/compact_merkle_tree.py
   state_proofs    GpuStateVerifier (+ verify_state_proofs_batch), sha3_256_batch
                   state/pruning_state.py, state/trie/pruning_trie.py
   state_store     GpuStateStore: a device-resident trie node store,
@@ -32,15 +35,19 @@ __version__ = '0.1.0'
 
 # exported from merkle_proofs, imported on first use (the package import stays light)
 _MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
+_LEDGER_TREE = ('GpuLedgerTree',)
 _STATE_PROOFS = ('GpuStateVerifier', 'verify_state_proofs_batch', 'sha3_256_batch')
 _STATE_STORE = ('GpuStateStore', 'state_root_batch')
-__all__ = list(_MERKLE_PROOFS + _STATE_PROOFS + _STATE_STORE)
+__all__ = list(_MERKLE_PROOFS + _LEDGER_TREE + _STATE_PROOFS + _STATE_STORE)
 
 
 def __getattr__(name):
     if name in _MERKLE_PROOFS:
         from . import merkle_proofs
         return getattr(merkle_proofs, name)
+    if name in _LEDGER_TREE:
+        from . import ledger_tree
+        return getattr(ledger_tree, name)
     if name in _STATE_PROOFS:
         from . import state_proofs
         return getattr(state_proofs, name)

@@ -85,6 +85,23 @@ SIGNATURES = [
     ('pv_merkle_tree_info', ctypes.c_int,
      [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), _vp]),
     ('pv_merkle_tree_free', ctypes.c_int, [ctypes.c_int32]),
+    ('pv_merkle_tree_stage', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp]),
+    ('pv_merkle_tree_stage_hashes', ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_uint64, _vp]),
+    ('pv_merkle_tree_stage_hashes_device', ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_uint64, _vp, _vp]),
+    ('pv_merkle_tree_commit', ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64]),
+    ('pv_merkle_tree_discard', ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, _vp]),
+    ('pv_merkle_tree_sizes', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    ('pv_merkle_tree_frontier', ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+    ('pv_merkle_tree_hash_store', ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ('pv_merkle_tree_hash_store_device', ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+      _vp]),
+    ('pv_merkle_tree_check_nodes', ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_uint64),
+      ctypes.POINTER(ctypes.c_uint64)]),
     ('pv_merkle_audit_paths', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
     ('pv_merkle_audit_paths_device', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     ('pv_merkle_consistency_proofs', ctypes.c_int, [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp]),

@@ -141,3 +141,13 @@ class ConsistencyError(VerifyError):
 
 class ProofError(VerifyError):
     """A cryptographic proof is not valid."""
+
+
+# Error contract of the ledger write cycle (ledger_tree.py).
+class LogicError(RuntimeError):
+    """Some logic assumption is wrong (common/exceptions.py:70-72; raised by
+    Ledger.discardTxns, plenum/common/ledger.py:113-115)."""
+
+
+class ConsistencyVerificationFailed(Exception):
+    """The hash store does not describe the tree (ledger/util.py:67-68)."""
