@@ -701,6 +701,55 @@ int pv_state_apply_device(int32_t store, const uint8_t *old_root, const uint8_t 
                           uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap,
                           uint64_t *node_off, uint64_t node_cap, uint8_t *digests, void *stream);
 
+/* State keys sorted on the device (csrc/pv_trie_sort.h), for keys that are produced there: the
+ * domain-state key of a NYM is sha256(nym) (plenum/server/request_handlers/utils.py:38-39,
+ * nym_handler.py:112), which pv_sha256_batch_device writes in request order.
+ *   Order: bytewise, a proper prefix first (the order the *_device forms above require).  Of equal
+ *   keys the occurrence with the highest index stays: the last of equal keys wins, as in the host
+ *   forms.  No input buffer is written and no value byte is read.
+ *   Cost: one round of radix passes per 8 bytes that two distinct keys share (1 round for random
+ *   32-byte keys).  Keys above 1024 bytes are refused (PV_EINVAL naming the first such key): the
+ *   host forms pv_state_build / pv_state_update / pv_state_apply sort keys of any length.
+ *   key_blob 4-byte aligned; keys may start at any byte; no byte past a key is read.
+ *   pv_state_sort_device
+ *            perm     DEVICE, n words out: perm[k] = the index of the k-th kept key, k < *n_kept;
+ *                     the rest is not written
+ *            n_kept   HOST out: the number of distinct keys
+ *            Refused by the first kernel with nothing written: key_off decreasing, a key above
+ *            1024 bytes.  n == 0: PV_OK, *n_kept = 0, nothing else is looked at.
+ *   pv_state_build_unsorted_device    the arguments of pv_state_build_device
+ *   pv_state_apply_unsorted_device    the arguments of pv_state_apply_device
+ *            The pairs in any order: the sort, a gather of the kept pairs into compact blobs, then
+ *            the code of the sorted form over them.  Every output, the sizing-call contract, insert
+ *            and n == 0 are those of the sorted form over the sorted distinct pairs, byte for byte;
+ *            in apply a later removal beats an earlier set and the other way round.  A batch
+ *            without removals gives pv_state_update_device's outputs.  The refusals before any
+ *            launch are the sorted form's; the first kernel refuses decreasing offsets, a key above
+ *            1024 bytes and a value that is above 2^30 bytes or (build) empty, naming the input
+ *            index, with nothing written and nothing inserted.
+ *            PV_EIO "device sort: a bug in the sort ...": the build's own order check refused the
+ *            sorted keys.  It is not retried. */
+int pv_state_sort_device(const uint8_t *key_blob, const uint64_t *key_off, uint64_t n, uint32_t *perm,
+                         uint64_t *n_kept, int device, void *stream);
+int pv_state_build_unsorted_device(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob,
+                                   const uint64_t *val_off, uint64_t n, int32_t store, uint8_t *root,
+                                   uint64_t *n_nodes, uint64_t *n_bytes, uint8_t *node_blob, uint64_t blob_cap,
+                                   uint64_t *node_off, uint64_t node_cap, uint8_t *digests, int device,
+                                   void *stream);
+int pv_state_apply_unsorted_device(int32_t store, const uint8_t *old_root, const uint8_t *key_blob,
+                                   const uint64_t *key_off, const uint8_t *val_blob, const uint64_t *val_off,
+                                   uint64_t n, int insert, uint8_t *new_root, uint64_t *n_nodes, uint64_t *n_bytes,
+                                   uint8_t *node_blob, uint64_t blob_cap, uint64_t *node_off, uint64_t node_cap,
+                                   uint8_t *digests, void *stream);
+
+/* Measurement only (tools/bench_state_sort.py): the first two steps of the fused forms over DEVICE
+ * pairs, the sort and the gather into the compact temporaries, each timed with HIP events on the
+ * call's stream; empty values are admitted, nothing is built.  HOST outputs: the kept count, the
+ * rounds the sort ran and the two times in milliseconds. */
+int pv_time_state_sort_device(const uint8_t *key_blob, const uint64_t *key_off, const uint8_t *val_blob,
+                              const uint64_t *val_off, uint64_t n, int device, void *stream, uint64_t *n_kept,
+                              uint32_t *rounds, float *ms_sort, float *ms_gather);
+
 /* Per-batch quorum tally, SURVEY.md §8(b) form (HOST memory).
  *   verdict_bits  n_batches x W words, W = ceil(n_nodes / 32): bit j of word w of
  *                 batch b = node 32 w + j cast a valid vote in batch b (a voter SET:

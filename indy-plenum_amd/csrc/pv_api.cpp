@@ -30,6 +30,7 @@
 #include "pv_trie_prune.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
+#include "pv_trie_sort.h"
 
 static_assert(pv::SP_OK == PV_SP_OK && pv::SP_VALUE_MISMATCH == PV_SP_VALUE_MISMATCH &&
                   pv::SP_NODE_MISSING == PV_SP_NODE_MISSING && pv::SP_MALFORMED == PV_SP_MALFORMED,
@@ -3809,9 +3810,202 @@ int sorted_pairs(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t
   return PV_OK;
 }
 
+// ------------------------------------------- the device sort (pv_trie_sort.h)
+// what k_trie_sort_init refused: hs[0 .. 2] = the first input index for offsets / key length / value
+int sort_refusal(const uint32_t* hs) {
+  if (hs[0] != 0xffffffffu) return fail(PV_EINVAL, "key_off or val_off decreases at index %u", hs[0]);
+  if (hs[1] != 0xffffffffu)
+    return fail(PV_EINVAL,
+                "key %u is above 1024 bytes: the device sort takes keys up to 1024 bytes, the host forms "
+                "(pv_state_build, pv_state_update, pv_state_apply) sort keys of any length",
+                hs[1]);
+  if (hs[2] != 0xffffffffu) return fail(PV_EINVAL, "value %u is empty or above 2^30 bytes", hs[2]);
+  return PV_OK;
+}
+
+// perm[0 .. *kept) = the input indices of the distinct keys in order, the last of equal keys kept
+// (device memory, n entries); val_off: checked with the keys when given (the fused forms).  Nothing
+// is written to perm when the first kernel refuses.  *rounds: the rounds run.  Ends synchronised.
+int sort_core(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, const uint64_t* vo, bool empty_ok,
+              uint64_t n, uint32_t* perm, uint64_t* kept, uint32_t* rounds = nullptr) {
+  const int mb = merkle_blocks(d);
+  const uint64_t table_words = 256 * pv::trie_sort_blocks(n);
+  TmpBuf<pv::TsRec> ra, rb;
+  TmpBuf<uint64_t> x, table;
+  TmpBuf<uint32_t> stats;
+  StreamDrain tail{s};
+  HIP_OK(ra.alloc(n));
+  HIP_OK(rb.alloc(n));
+  HIP_OK(x.alloc(n + 1));
+  HIP_OK(table.alloc(table_words));
+  uint32_t hs[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+  HIP_OK(stats.put(hs, 3, s));
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(table_words > n + 1 ? table_words : n + 1)));
+  HIP_OK(pv::launch_trie_sort_init(kb, ko, vo, empty_ok, n, ra.p, stats.p, mb, s));
+  HIP_OK(hipMemcpyAsync(hs, stats.p, 12, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (const int rc = sort_refusal(hs)) return rc;
+  pv::TsRec *cur = ra.p, *other = rb.p;
+  uint64_t runs = 1;
+  uint32_t r = 0;
+  for (;; ++r) {
+    if (r >= pv::TS_MAX_ROUNDS) return fail(PV_EIO, "device sort: keys unresolved after %u rounds", r);
+    if (r > 0) {   // the segment of round r is the run's rank after round r - 1
+      HIP_OK(pv::launch_trie_sort_round(kb, ko, cur, x.p, n, r, other, mb, s));
+      std::swap(cur, other);
+    }
+    const uint32_t passes = 9 + (r > 0 ? pv::ts_seg_digits(runs) : 0);
+    for (uint32_t p = 0; p < passes; ++p) {
+      HIP_OK(pv::launch_trie_sort_pass(cur, n, p, table.p, d.scan.p, other, s));
+      std::swap(cur, other);
+    }
+    HIP_OK(pv::launch_trie_sort_flags(cur, n, x.p, mb, s));
+    HIP_OK(pv::launch_exclusive_scan(x.p, n + 1, d.scan.p, s));
+    uint64_t totals = 0;   // unresolved << 32 | runs
+    HIP_OK(hipMemcpyAsync(&totals, x.p + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    runs = totals & 0xffffffffull;
+    if (runs == 0 || runs > n) return fail(PV_EIO, "device sort: inconsistent flag pass");
+    if ((totals >> 32) == 0) break;
+  }
+  HIP_OK(pv::launch_trie_sort_finish(cur, x.p, n, perm, mb, s));
+  *kept = runs;
+  if (rounds) *rounds = r + 1;
+  return tail.finish();
+}
+
+// The fused forms' input: device pairs in any order -> the pairs sorted with the last of equal
+// keys kept, as blobs with 16 spare bytes and offsets from 0 (what sorted_pairs gives the host forms).
+struct DevicePairs {
+  TmpBuf<uint8_t> kb, vb;
+  TmpBuf<uint64_t> ko, vo;
+  uint64_t m = 0;
+};
+
+int sort_pairs_device(Device& d, hipStream_t s, const uint8_t* kb, const uint64_t* ko, const uint8_t* vb,
+                      const uint64_t* vo, uint64_t n, bool empty_ok, DevicePairs& out, uint32_t* rounds = nullptr,
+                      hipEvent_t sorted = nullptr) {
+  const int mb = merkle_blocks(d);
+  TmpBuf<uint32_t> perm;
+  StreamDrain tail{s};
+  HIP_OK(perm.alloc(n));
+  if (const int rc = sort_core(d, s, kb, ko, vo, empty_ok, n, perm.p, &out.m, rounds)) return rc;
+  if (sorted) HIP_OK(hipEventRecord(sorted, s));   // pv_time_state_sort_device: the sort ends, the gather begins
+  const uint64_t m = out.m;
+  HIP_OK(out.ko.alloc(m + 1));
+  HIP_OK(out.vo.alloc(m + 1));
+  HIP_OK(pv::launch_trie_sort_lens(perm.p, m, n, ko, vo, out.ko.p, out.vo.p, mb, s));
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(m + 1)));
+  HIP_OK(pv::launch_exclusive_scan(out.ko.p, m + 1, d.scan.p, s));
+  HIP_OK(pv::launch_exclusive_scan(out.vo.p, m + 1, d.scan.p, s));
+  uint64_t kbytes = 0, vbytes = 0;
+  HIP_OK(hipMemcpyAsync(&kbytes, out.ko.p + m, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&vbytes, out.vo.p + m, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  HIP_OK(out.kb.alloc(kbytes + 16));
+  HIP_OK(out.vb.alloc(vbytes + 16));
+  HIP_OK(hipMemsetAsync(out.kb.p + kbytes, 0, 16, s));
+  HIP_OK(hipMemsetAsync(out.vb.p + vbytes, 0, 16, s));
+  HIP_OK(pv::launch_trie_sort_copy(perm.p, m, n, kb, ko, vb, vo, out.ko.p, out.vo.p, out.kb.p, out.vb.p, mb, s));
+  return tail.finish();
+}
+
+// The build's first kernel checks the order again.  After the device sort that refusal is a bug
+// in the sort, not in the caller's input: it is reported as one, and nothing is retried.
+int sort_selfcheck(int rc) {
+  if (rc == PV_EINVAL && g_err.compare(0, 28, "keys not strictly increasing") == 0) {
+    const std::string was = g_err;
+    return fail(PV_EIO, "device sort: a bug in the sort, its output was refused by the build (%s)", was.c_str());
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The permutation that sorts state keys: bytewise, a proper prefix first, the last of equal keys
+// kept (csrc/pv_trie_sort.h); see include/plenum_verify.h.
+int pv_state_sort_device(const uint8_t* key_blob, const uint64_t* key_off, uint64_t n, uint32_t* perm,
+                         uint64_t* n_kept, int device, void* stream) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (n == 0) {
+    if (n_kept) *n_kept = 0;
+    return PV_OK;
+  }
+  if (!n_kept) return fail(PV_EINVAL, "null pointer");
+  if (!key_blob || !key_off || !perm) return fail(PV_EINVAL, "null device buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  if (reinterpret_cast<uintptr_t>(key_blob) & 3u) return fail(PV_EINVAL, "key_blob must be 4-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  *n_kept = 0;
+  return sort_core(*en.d, en.s, key_blob, key_off, nullptr, true, n, perm, n_kept);
+}
+
+// pv_state_build_device over pairs in any order, the last of equal keys winning: the device sort,
+// the gather, then the same build; see include/plenum_verify.h.
+int pv_state_build_unsorted_device(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
+                                   const uint64_t* val_off, uint64_t n, int32_t store, uint8_t* root,
+                                   uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap,
+                                   uint64_t* node_off, uint64_t node_cap, uint8_t* digests, int device, void* stream) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (n == 0) return build_empty(en, stream, root, n_nodes, n_bytes, node_off, false);
+  if (!root) return fail(PV_EINVAL, "null pointer");
+  if (!key_blob || !key_off || !val_blob || !val_off) return fail(PV_EINVAL, "null device buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  if ((reinterpret_cast<uintptr_t>(key_blob) & 3u) || (reinterpret_cast<uintptr_t>(val_blob) & 3u))
+    return fail(PV_EINVAL, "key_blob and val_blob must be 4-byte aligned");
+  if (digests && misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
+  StateStore* st = nullptr;
+  if (store != -1) {
+    st = find_store(store);
+    if (!st) return fail(PV_EINVAL, "no state store with id %d", (int)store);
+    if (st->dev != en.d->id)
+      return fail(PV_EINVAL, "state store %d lives on device %d, not on device %d", (int)store, st->dev, device);
+  }
+  if (const int rc = en.begin(stream)) return rc;
+  if (n_nodes) *n_nodes = 0;
+  if (n_bytes) *n_bytes = 0;
+  DevicePairs sp;
+  StreamDrain tail{en.s};
+  if (const int rc = sort_pairs_device(*en.d, en.s, key_blob, key_off, val_blob, val_off, n, false, sp)) return rc;
+  return sort_selfcheck(build_core(*en.d, en.s, sp.kb.p, sp.ko.p, sp.vb.p, sp.vo.p, sp.m, st, root, n_nodes, n_bytes,
+                                   node_blob, blob_cap, node_off, node_cap, digests, false));
+}
+
+// The sort and the gather of the fused forms alone, each timed with HIP events on the call's
+// stream (tools/bench_state_sort.py); see include/plenum_verify.h.
+int pv_time_state_sort_device(const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
+                              const uint64_t* val_off, uint64_t n, int device, void* stream, uint64_t* n_kept,
+                              uint32_t* rounds, float* ms_sort, float* ms_gather) {
+  Entry en(device);
+  if (const int rc = en.check()) return rc;
+  if (!n_kept || !rounds || !ms_sort || !ms_gather) return n == 0 ? PV_OK : fail(PV_EINVAL, "null pointer");
+  *n_kept = 0;
+  *rounds = 0;
+  *ms_sort = *ms_gather = 0;
+  if (n == 0) return PV_OK;
+  if (!key_blob || !key_off || !val_blob || !val_off) return fail(PV_EINVAL, "null device buffer");
+  if (n > pv::TB_MAX_KEYS) return fail(PV_EINVAL, "more than 2^28 keys in one build");
+  if ((reinterpret_cast<uintptr_t>(key_blob) & 3u) || (reinterpret_cast<uintptr_t>(val_blob) & 3u))
+    return fail(PV_EINVAL, "key_blob and val_blob must be 4-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  PhaseEvents ev;
+  HIP_OK(ev.create());
+  DevicePairs sp;
+  StreamDrain tail{en.s};
+  HIP_OK(ev.mark(0, en.s));
+  if (const int rc = sort_pairs_device(*en.d, en.s, key_blob, key_off, val_blob, val_off, n, true, sp, rounds, ev.ev[1]))
+    return rc;
+  HIP_OK(ev.mark(2, en.s));
+  HIP_OK(hipEventSynchronize(ev.ev[2]));
+  HIP_OK(hipEventElapsedTime(ms_sort, ev.ev[0], ev.ev[1]));
+  HIP_OK(hipEventElapsedTime(ms_gather, ev.ev[1], ev.ev[2]));
+  *n_kept = sp.m;
+  return tail.finish();
+}
 
 // PruningState.set per pair and headHash (state/pruning_state.py:60-61, 136; Trie.update,
 // state/trie/pruning_trie.py:1006-1027) as one batch; see include/plenum_verify.h.
@@ -4063,7 +4257,7 @@ int update_empty(Entry& en, void* stream, const uint8_t* old_root, uint8_t* new_
 int update_device_entry(int32_t store, const uint8_t* old_root, const uint8_t* key_blob, const uint64_t* key_off,
                         const uint8_t* val_blob, const uint64_t* val_off, uint64_t n, int insert, uint8_t* new_root,
                         uint64_t* n_nodes, uint64_t* n_bytes, uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off,
-                        uint64_t node_cap, uint8_t* digests, void* stream, bool removals) {
+                        uint64_t node_cap, uint8_t* digests, void* stream, bool removals, bool unsorted = false) {
   Entry en;
   if (n == 0) {   // as the empty build: nothing is looked at, the store included
     if (const int rc = en.check()) return rc;
@@ -4078,6 +4272,16 @@ int update_device_entry(int32_t store, const uint8_t* old_root, const uint8_t* k
     return fail(PV_EINVAL, "key_blob and val_blob must be 4-byte aligned");
   if (digests && misaligned16(digests)) return fail(PV_EINVAL, "digest buffers must be 16-byte aligned");
   if (const int rc = en.begin(stream)) return rc;
+  if (unsorted) {   // pv_state_apply_unsorted_device: the device sort and the gather first
+    if (n_nodes) *n_nodes = 0;
+    if (n_bytes) *n_bytes = 0;
+    DevicePairs sp;
+    StreamDrain tail{en.s};
+    if (const int rc = sort_pairs_device(*en.d, en.s, key_blob, key_off, val_blob, val_off, n, removals, sp)) return rc;
+    return sort_selfcheck(update_core(*en.d, en.s, *st, old_root, sp.kb.p, sp.ko.p, sp.vb.p, sp.vo.p, sp.m, insert != 0,
+                                      new_root, n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap, digests,
+                                      false, removals));
+  }
   return update_core(*en.d, en.s, *st, old_root, key_blob, key_off, val_blob, val_off, n, insert != 0, new_root,
                      n_nodes, n_bytes, node_blob, blob_cap, node_off, node_cap, digests, false, removals);
 }
@@ -4149,6 +4353,18 @@ int pv_state_apply_device(int32_t store, const uint8_t* old_root, const uint8_t*
                           uint64_t* node_off, uint64_t node_cap, uint8_t* digests, void* stream) {
   return update_device_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
                              n_bytes, node_blob, blob_cap, node_off, node_cap, digests, stream, true);
+}
+
+// pv_state_apply_device over pairs in any order, the last of equal keys winning (a later removal
+// over an earlier set as a later set over an earlier removal): the device sort, the gather, then
+// the same apply; see include/plenum_verify.h.
+int pv_state_apply_unsorted_device(int32_t store, const uint8_t* old_root, const uint8_t* key_blob,
+                                   const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
+                                   uint64_t n, int insert, uint8_t* new_root, uint64_t* n_nodes, uint64_t* n_bytes,
+                                   uint8_t* node_blob, uint64_t blob_cap, uint64_t* node_off, uint64_t node_cap,
+                                   uint8_t* digests, void* stream) {
+  return update_device_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
+                             n_bytes, node_blob, blob_cap, node_off, node_cap, digests, stream, true, true);
 }
 
 // The host form of the same (state/pruning_state.py:60-61, 84-85; state/trie/pruning_trie.py:683-848,

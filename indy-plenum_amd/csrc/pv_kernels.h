@@ -287,6 +287,28 @@ hipError_t launch_trie_update_emit(const TuCtx& c, int max_blocks, hipStream_t s
 hipError_t launch_trie_apply_count(const TuCtx& c, int max_blocks, hipStream_t s);
 hipError_t launch_trie_apply_emit(const TuCtx& c, int max_blocks, hipStream_t s);
 
+// sorting state keys (pv_trie_sort.h): the first kernel's checks, one LSD pass, the flag pass,
+// perm, and the gather of the kept pairs into compact blobs
+struct TsRec;
+uint64_t trie_sort_blocks(uint64_t n);
+hipError_t launch_trie_sort_init(const uint8_t* key_blob, const uint64_t* key_off, const uint64_t* val_off,
+                                 bool empty_ok, uint64_t n, TsRec* rec, uint32_t* stats, int max_blocks,
+                                 hipStream_t s);
+hipError_t launch_trie_sort_round(const uint8_t* key_blob, const uint64_t* key_off, const TsRec* in, const uint64_t* x,
+                                  uint64_t n, uint32_t r, TsRec* out, int max_blocks, hipStream_t s);
+hipError_t launch_trie_sort_pass(const TsRec* in, uint64_t n, uint32_t p, uint64_t* table, uint64_t* sums, TsRec* out,
+                                 hipStream_t s);
+hipError_t launch_trie_sort_flags(const TsRec* rec, uint64_t n, uint64_t* x, int max_blocks, hipStream_t s);
+hipError_t launch_trie_sort_finish(const TsRec* rec, const uint64_t* x, uint64_t n, uint32_t* perm, int max_blocks,
+                                   hipStream_t s);
+hipError_t launch_trie_sort_lens(const uint32_t* perm, uint64_t m, uint64_t n, const uint64_t* key_off,
+                                 const uint64_t* val_off, uint64_t* klen, uint64_t* vlen, int max_blocks,
+                                 hipStream_t s);
+hipError_t launch_trie_sort_copy(const uint32_t* perm, uint64_t m, uint64_t n, const uint8_t* key_blob,
+                                 const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
+                                 const uint64_t* out_koff, const uint64_t* out_voff, uint8_t* out_keys,
+                                 uint8_t* out_vals, int max_blocks, hipStream_t s);
+
 // deterministic synthetic workload; spec in plenum_gpu/synth.py.
 // mode 0 FIXED (len = mlen_min), 1 RANGE (len uniform in [mlen_min, mlen_max]),
 // 2 COMMIT (C3 3PC batches of n_nodes votes).

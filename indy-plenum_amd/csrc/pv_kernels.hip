@@ -23,6 +23,7 @@
 #include "pv_trie_prune.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
+#include "pv_trie_sort.h"
 #include "pv_kernels.h"
 #include "plenum_verify.h"
 
@@ -2221,6 +2222,218 @@ hipError_t launch_trie_apply_count(const TuCtx& c, int max_blocks, hipStream_t s
 hipError_t launch_trie_apply_emit(const TuCtx& c, int max_blocks, hipStream_t s) {
   if (c.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_trie_apply_emit, dim3(mp_grid(c.n, max_blocks)), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- sorting state keys
+// pv_trie_sort.h: the per-item routines are the header's; here are the grids.
+// stats[0 .. 2] = the first input index refused for its offsets / its key's
+// length / its value (0xffffffff: none).  No key byte of a refused input is read.
+__global__ __launch_bounds__(256) void k_trie_sort_init(const uint8_t* __restrict__ key_blob,
+                                                        const uint64_t* __restrict__ key_off,
+                                                        const uint64_t* __restrict__ val_off, uint32_t empty_ok,
+                                                        uint64_t n, TsRec* __restrict__ rec,
+                                                        uint32_t* __restrict__ stats) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const uint32_t bad = ts_check_one(key_off, val_off, i, empty_ok != 0);
+    if (bad & TS_BAD_OFFSET) atomicMin(stats, (uint32_t)i);
+    if (bad & TS_BAD_LENGTH) atomicMin(stats + 1, (uint32_t)i);
+    if (bad & TS_BAD_VALUE) atomicMin(stats + 2, (uint32_t)i);
+    TsRec x;
+    x.word = 0;
+    x.sv = 0;
+    x.idx = (uint32_t)i;
+    rec[i] = (bad & (TS_BAD_OFFSET | TS_BAD_LENGTH)) ? x : ts_make(key_blob, key_off, (uint32_t)i, 0, 0);
+  }
+}
+
+// round r >= 1: position k keeps its key and takes its run's rank as the segment
+__global__ __launch_bounds__(256) void k_trie_sort_round(const uint8_t* __restrict__ key_blob,
+                                                         const uint64_t* __restrict__ key_off,
+                                                         const TsRec* __restrict__ in, const uint64_t* __restrict__ x,
+                                                         uint64_t n, uint32_t r, TsRec* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += stride) {
+    const uint32_t idx = in[k].idx;
+    if (idx < n) out[k] = ts_make(key_blob, key_off, idx, ts_rank(x, k), r);   // always: idx is a permutation
+  }
+}
+
+// table[digit * blocks + block] = the tile's records with that digit in pass p
+__global__ __launch_bounds__(TS_BLOCK) void k_trie_sort_hist(const TsRec* __restrict__ rec, uint64_t n, uint32_t p,
+                                                             uint64_t* __restrict__ table, uint64_t blocks) {
+  __shared__ uint32_t hist[256];
+  const uint32_t t = threadIdx.x;
+  hist[t] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * TS_TILE;
+  for (uint32_t k = 0; k < TS_ITEMS; ++k) {
+    const uint64_t pos = base + k * TS_BLOCK + t;
+    if (pos < n) atomicAdd(&hist[ts_digit(rec[pos], p)], 1u);
+  }
+  __syncthreads();
+  table[(uint64_t)t * blocks + blockIdx.x] = hist[t];
+}
+
+// The stable scatter of pass p (pv_trie_sort.h): table holds the exclusive scan of the histograms.
+__global__ __launch_bounds__(TS_BLOCK) void k_trie_sort_scatter(const TsRec* __restrict__ in, uint64_t n, uint32_t p,
+                                                                const uint64_t* __restrict__ table, uint64_t blocks,
+                                                                TsRec* __restrict__ out) {
+  __shared__ uint32_t run[256];        // the next slot of each digit
+  __shared__ uint32_t wcnt[4][256];    // the chunk's records of each digit, per wave
+  const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63u;
+  run[t] = (uint32_t)table[(uint64_t)t * blocks + blockIdx.x];
+  for (uint32_t q = 0; q < 4; ++q) wcnt[q][t] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * TS_TILE;
+  for (uint32_t k = 0; k < TS_ITEMS; ++k) {
+    const uint64_t pos = base + k * TS_BLOCK + t;
+    const bool live = pos < n;
+    TsRec x;
+    x.word = 0;
+    x.sv = 0;
+    x.idx = 0;
+    if (live) x = in[pos];
+    const uint32_t d = live ? ts_digit(x, p) : 0;
+    unsigned long long same = __ballot(live);   // the live lanes of this wave with my digit
+    for (uint32_t bit = 0; bit < 8; ++bit) {
+      const bool on = (d >> bit) & 1u;
+      const unsigned long long b = __ballot(on);
+      same &= on ? b : ~b;
+    }
+    const uint32_t below = (uint32_t)__popcll(same & ((1ull << lane) - 1));
+    if (live && below == 0) wcnt[w][d] = (uint32_t)__popcll(same);
+    __syncthreads();
+    if (live) {
+      uint32_t o = run[d] + below;
+      for (uint32_t q = 0; q < w; ++q) o += wcnt[q][d];
+      if (o < n) out[o] = x;   // always: the histogram counted these records
+    }
+    __syncthreads();
+    uint32_t sum = 0;
+    for (uint32_t q = 0; q < 4; ++q) {
+      sum += wcnt[q][t];
+      wcnt[q][t] = 0;
+    }
+    run[t] += sum;
+    __syncthreads();
+  }
+}
+
+// x[k] = the flag word of position k, x[n] = 0: scanned, x[n] is (unresolved << 32 | runs)
+__global__ __launch_bounds__(256) void k_trie_sort_flags(const TsRec* __restrict__ rec, uint64_t n,
+                                                         uint64_t* __restrict__ x) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k <= n; k += stride)
+    x[k] = k < n ? ts_flag_one(rec, n, k) : 0;
+}
+
+// the last key of every run, at its run's rank
+__global__ __launch_bounds__(256) void k_trie_sort_finish(const TsRec* __restrict__ rec, const uint64_t* __restrict__ x,
+                                                          uint64_t n, uint32_t* __restrict__ perm) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += stride)
+    if (ts_keep_one(rec, n, k)) {
+      const uint32_t at = ts_rank(x, k);
+      if (at < n) perm[at] = rec[k].idx;   // always: a rank is below the run count
+    }
+}
+
+// klen[k] / vlen[k] = the lengths of kept pair k (m + 1 entries, the last 0: scanned to the offsets)
+__global__ __launch_bounds__(256) void k_trie_sort_lens(const uint32_t* __restrict__ perm, uint64_t m, uint64_t n,
+                                                        const uint64_t* __restrict__ key_off,
+                                                        const uint64_t* __restrict__ val_off,
+                                                        uint64_t* __restrict__ klen, uint64_t* __restrict__ vlen) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k <= m; k += stride) {
+    const uint64_t i = k < m ? perm[k] : n;
+    klen[k] = i < n ? key_off[i + 1] - key_off[i] : 0;   // i < n always for k < m: perm holds input indices
+    vlen[k] = i < n ? val_off[i + 1] - val_off[i] : 0;
+  }
+}
+
+// One wave per kept pair; lanes stride over the key's and the value's bytes.
+__global__ __launch_bounds__(256) void k_trie_sort_copy(const uint32_t* __restrict__ perm, uint64_t m, uint64_t n,
+                                                        const uint8_t* __restrict__ key_blob,
+                                                        const uint64_t* __restrict__ key_off,
+                                                        const uint8_t* __restrict__ val_blob,
+                                                        const uint64_t* __restrict__ val_off,
+                                                        const uint64_t* __restrict__ out_koff,
+                                                        const uint64_t* __restrict__ out_voff,
+                                                        uint8_t* __restrict__ out_keys, uint8_t* __restrict__ out_vals) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t k = wave; k < m; k += waves) {
+    const uint64_t i = perm[k];
+    if (i >= n) continue;   // never: perm holds input indices
+    const uint64_t ks = key_off[i], kl = out_koff[k + 1] - out_koff[k], kd = out_koff[k];
+    for (uint64_t b = lane; b < kl; b += 64) out_keys[kd + b] = key_blob[ks + b];
+    const uint64_t vs = val_off[i], vl = out_voff[k + 1] - out_voff[k], vd = out_voff[k];
+    for (uint64_t b = lane; b < vl; b += 64) out_vals[vd + b] = val_blob[vs + b];
+  }
+}
+
+uint64_t trie_sort_blocks(uint64_t n) { return (n + TS_TILE - 1) / TS_TILE; }
+
+hipError_t launch_trie_sort_init(const uint8_t* key_blob, const uint64_t* key_off, const uint64_t* val_off,
+                                 bool empty_ok, uint64_t n, TsRec* rec, uint32_t* stats, int max_blocks,
+                                 hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_sort_init, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, key_blob, key_off, val_off,
+                     empty_ok ? 1u : 0u, n, rec, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_sort_round(const uint8_t* key_blob, const uint64_t* key_off, const TsRec* in, const uint64_t* x,
+                                  uint64_t n, uint32_t r, TsRec* out, int max_blocks, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_sort_round, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, key_blob, key_off, in, x, n, r,
+                     out);
+  return hipGetLastError();
+}
+
+// one LSD pass: in -> out by digit p; table: 256 * trie_sort_blocks(n) words, sums: scan_sums_words of that
+hipError_t launch_trie_sort_pass(const TsRec* in, uint64_t n, uint32_t p, uint64_t* table, uint64_t* sums, TsRec* out,
+                                 hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint64_t blocks = trie_sort_blocks(n);
+  hipLaunchKernelGGL(k_trie_sort_hist, dim3((uint32_t)blocks), dim3(TS_BLOCK), 0, s, in, n, p, table, blocks);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_exclusive_scan(table, 256 * blocks, sums, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_trie_sort_scatter, dim3((uint32_t)blocks), dim3(TS_BLOCK), 0, s, in, n, p, table, blocks, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_sort_flags(const TsRec* rec, uint64_t n, uint64_t* x, int max_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_trie_sort_flags, dim3(mp_grid(n + 1, max_blocks)), dim3(256), 0, s, rec, n, x);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_sort_finish(const TsRec* rec, const uint64_t* x, uint64_t n, uint32_t* perm, int max_blocks,
+                                   hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_sort_finish, dim3(mp_grid(n, max_blocks)), dim3(256), 0, s, rec, x, n, perm);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_sort_lens(const uint32_t* perm, uint64_t m, uint64_t n, const uint64_t* key_off,
+                                 const uint64_t* val_off, uint64_t* klen, uint64_t* vlen, int max_blocks,
+                                 hipStream_t s) {
+  hipLaunchKernelGGL(k_trie_sort_lens, dim3(mp_grid(m + 1, max_blocks)), dim3(256), 0, s, perm, m, n, key_off,
+                     val_off, klen, vlen);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_sort_copy(const uint32_t* perm, uint64_t m, uint64_t n, const uint8_t* key_blob,
+                                 const uint64_t* key_off, const uint8_t* val_blob, const uint64_t* val_off,
+                                 const uint64_t* out_koff, const uint64_t* out_voff, uint8_t* out_keys,
+                                 uint8_t* out_vals, int max_blocks, hipStream_t s) {
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_sort_copy, dim3(mp_grid(m * 64, max_blocks)), dim3(256), 0, s, perm, m, n, key_blob,
+                     key_off, val_blob, val_off, out_koff, out_voff, out_keys, out_vals);
   return hipGetLastError();
 }
 

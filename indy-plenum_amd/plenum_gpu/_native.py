@@ -155,6 +155,20 @@ SIGNATURES = [
      [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
       ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
       ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp]),
+    # the device sort of state keys: perm DEVICE, n_kept a typed HOST out-parameter
+    ('pv_state_sort_device', ctypes.c_int,
+     [_vp, _vp, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, _vp]),
+    # as pv_state_build_device / pv_state_apply_device; pairs in any order, the last of equal keys wins
+    ('pv_state_build_unsorted_device', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64),
+      ctypes.POINTER(ctypes.c_uint64), _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, ctypes.c_int, _vp]),
+    ('pv_state_apply_unsorted_device', ctypes.c_int,
+     [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), _vp,
+      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp]),
+    ('pv_time_state_sort_device', ctypes.c_int,
+     [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_uint64),
+      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     ('pv_state_store_prove', ctypes.c_int,
      [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
       _vp, ctypes.c_uint64]),

@@ -59,6 +59,13 @@ reference would return [b''].
   (state/trie/pruning_trie.py:208-230, 681; state/db/refcount_db.py); here the caller names the
   roots.  `reachable_host(db, roots)` is the pure-Python mirror of the mark.
 
+* `sort_keys_gpu(keys)` -- pv_state_sort_device (csrc/pv_trie_sort.h): the permutation that sorts
+  state keys on the device, the last of equal keys kept; `sort_keys_host(keys)` is its mirror.
+  `build_state(items, device_sort=True)` and `apply_batch(root, items, device_sort=True)` upload the
+  pairs in the caller's order (pv_state_build_unsorted_device, pv_state_apply_unsorted_device), and
+  `apply_batch_sha256(root, items)` hashes NYM-style preimages into the key buffer on the device
+  first, so no key crosses back to the host.
+
 Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal).
 """
 import ctypes
@@ -753,6 +760,103 @@ def _apply_gpu(store_id, root, pairs, insert=True, want_nodes=False):
     return _update_gpu(store_id, root, pairs, insert, want_nodes, entry='pv_state_apply')
 
 
+# ------------------------------------------------------------------ keys sorted on the device
+SORT_TILE = 2048            # csrc/pv_trie_sort.h: TS_TILE, the scatter kernel's items per block
+SORT_MAX_KEY_BYTES = 1024   # TS_MAX_KEY_BYTES: longer keys are refused by the device sort
+
+
+def sort_keys_host(keys):
+    """The mirror of pv_state_sort_device: perm (uint32) with perm[k] = the index of the k-th key in
+    bytewise order, a proper prefix first; of equal keys the last occurrence stays."""
+    last = {}
+    for i, key in enumerate(keys):
+        last[bytes(key)] = i
+    return np.array([last[k] for k in sorted(last)], np.uint32)
+
+
+def _encoded_in_order(items, removals):
+    """(key, raw value or None) pairs -> [(key, rlp([value]) or b'' for a removal)] in the caller's
+    order, every occurrence kept: what the fused forms sort and deduplicate on the device"""
+    out = []
+    for key, value in items:
+        key = key.encode() if isinstance(key, str) else bytes(key)
+        if value is None and removals:
+            out.append((key, b''))
+            continue
+        value = value.encode() if isinstance(value, str) else bytes(value)
+        if not value:
+            raise ValueError('an empty value is no value; None removes a key' if removals else
+                             'an empty value removes a key; a build takes values only')
+        out.append((key, rlp_encode([value])))
+    return out
+
+
+def _upload(arr, device):
+    """a numpy array as a device tensor of its bytes plus the 16 spare bytes the kernels may read"""
+    import torch
+    raw = np.concatenate([np.ascontiguousarray(arr).view(np.uint8).reshape(-1), np.zeros(16, np.uint8)])
+    return torch.from_numpy(raw).to(torch.device('cuda', device))
+
+
+def _dp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def sort_keys_gpu(keys, device=0):
+    """pv_state_sort_device over `keys` (uploaded as they are) -> perm as sort_keys_host gives it"""
+    nat.ensure_init()
+    keys = [bytes(k) for k in keys]
+    n = len(keys)
+    if n == 0:
+        return np.zeros(0, np.uint32)
+    import torch
+    kblob, koff = nat.pack_messages(keys)
+    d_kb, d_ko = _upload(kblob, device), _upload(koff, device)
+    perm = torch.zeros(4 * n, dtype=torch.uint8, device=d_kb.device)
+    kept = ctypes.c_uint64(0)
+    torch.cuda.synchronize(d_kb.device)   # the library runs on its own stream
+    nat._check('pv_state_sort_device',
+               nat.load().pv_state_sort_device(_dp(d_kb), _dp(d_ko), n, _dp(perm), ctypes.byref(kept), device, None))
+    return perm.cpu().numpy().view(np.uint32)[:kept.value].copy()
+
+
+def _build_unsorted_gpu(pairs, store_id, device=0):
+    """pv_state_build_unsorted_device over (key, encoded value) pairs in any order -> (root, n_nodes, n_bytes)"""
+    nat.ensure_init()
+    n = len(pairs)
+    kblob, koff = nat.pack_messages([k for k, _ in pairs])
+    vblob, voff = nat.pack_messages([v for _, v in pairs])
+    bufs = [_upload(a, device) for a in (kblob, koff, vblob, voff)] if n else [None] * 4
+    root = np.zeros(32, np.uint8)
+    nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    nat._check('pv_state_build_unsorted_device', nat.load().pv_state_build_unsorted_device(
+        *[_dp(b) if n else None for b in bufs], n, store_id, _root_ptr(root), ctypes.byref(nn), ctypes.byref(nb),
+        None, 0, None, 0, None, device, None))
+    return root.tobytes(), nn.value, nb.value
+
+
+def _apply_unsorted_device(store_id, root, n, d_kb, d_ko, d_vb, d_vo, insert=True):
+    """pv_state_apply_unsorted_device over device tensors -> (new root, n_nodes, n_bytes)"""
+    old = np.frombuffer(bytes(root), np.uint8).copy()
+    new = np.zeros(32, np.uint8)
+    nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    nat._check('pv_state_apply_unsorted_device', nat.load().pv_state_apply_unsorted_device(
+        store_id, _root_ptr(old), _dp(d_kb), _dp(d_ko), _dp(d_vb), _dp(d_vo), n, int(insert), _root_ptr(new),
+        ctypes.byref(nn), ctypes.byref(nb), None, 0, None, 0, None, None))
+    return new.tobytes(), nn.value, nb.value
+
+
+def _apply_unsorted_gpu(store_id, root, pairs, device=0, insert=True):
+    """pv_state_apply_unsorted_device over (key, encoded value or b'') pairs in any order"""
+    nat.ensure_init()
+    if not pairs:
+        return bytes(root), 0, 0
+    kblob, koff = nat.pack_messages([k for k, _ in pairs])
+    vblob, voff = nat.pack_messages([v for _, v in pairs])
+    bufs = [_upload(a, device) for a in (kblob, koff, vblob, voff)]
+    return _apply_unsorted_device(store_id, root, len(pairs), *bufs, insert=insert)
+
+
 def state_root_batch(items):
     """The state root after PruningState.set of every (key, raw value) pair (state/pruning_state.py
     :60-61), the last of equal keys winning; no node is kept.  One pv_state_build call from
@@ -882,10 +986,13 @@ class GpuStateStore:
         dropped)."""
         return self._prune(keep_roots, 1, want_digests)
 
-    def build_state(self, items):
+    def build_state(self, items, device_sort=False):
         """Build the trie of (key, raw value) pairs on the device (pv_state_build) and insert its
         nodes -> the root hash.  Afterwards generate_state_proof(key, root, ...) and
-        get_for_root_hash_batch work at that root; no host trie is involved."""
+        get_for_root_hash_batch work at that root; no host trie is involved.  With device_sort the
+        pairs are uploaded in the caller's order and sorted there (pv_state_build_unsorted_device)."""
+        if device_sort:
+            return _build_unsorted_gpu(_encoded_in_order(items, False), self._id, self.device)[0]
         return _build_gpu(_pairs(items), self._id)[0]
 
     def update_state(self, root, items):
@@ -903,16 +1010,49 @@ class GpuStateStore:
                 raise (KeyError if 'is not in the store' in text else ValueError)(text) from None
             raise
 
-    def apply_batch(self, root, items):
+    def apply_batch(self, root, items, device_sort=False):
         """Apply (key, raw value or None) pairs to the state at the committed `root` on the device
         (pv_state_apply) and insert the nodes it emits -> the new root hash: one 3PC batch of
         PruningState.set and, for a value of None, PruningState.remove (state/pruning_state.py:60-61,
         84-85), the last of equal keys winning.  Removing a key the state does not hold changes
         nothing; removing every key gives BLANK_ROOT.  `root` and every earlier root stay provable.
         KeyError when the root, a node on a key's path or a node referenced from a branch on a
-        removed key's path is not in the store, ValueError for a node that is no trie node."""
+        removed key's path is not in the store, ValueError for a node that is no trie node.  With
+        device_sort the pairs are uploaded in the caller's order and sorted there
+        (pv_state_apply_unsorted_device)."""
         try:
+            if device_sort:
+                return _apply_unsorted_gpu(self._id, root_hash_of(root), _encoded_in_order(items, True),
+                                           self.device)[0]
             return _apply_gpu(self._id, root_hash_of(root), _ops(items))[0]
+        except nat.PlenumGpuError as exc:
+            text = str(exc)
+            if 'state apply: key ' in text:
+                raise (KeyError if 'is not in the store' in text else ValueError)(text) from None
+            raise
+
+    def apply_batch_sha256(self, root, items):
+        """apply_batch for (preimage, raw value or None) pairs whose state key is sha256(preimage),
+        as the domain state keys a NYM (nym_to_state_key, plenum/server/request_handlers/utils.py
+        :38-39; nym_handler.py:112).  pv_sha256_batch_device hashes the preimages into a device
+        buffer in request order and pv_state_apply_unsorted_device sorts and applies them there: no
+        key crosses back to the host."""
+        import torch
+        nat.ensure_init()
+        enc = _encoded_in_order(items, True)
+        n = len(enc)
+        if n == 0:
+            return root_hash_of(root)
+        pblob, poff = nat.pack_messages([k for k, _ in enc])
+        vblob, voff = nat.pack_messages([v for _, v in enc])
+        d_pb, d_po, d_vb, d_vo = (_upload(a, self.device) for a in (pblob, poff, vblob, voff))
+        d_keys = torch.zeros(32 * n + 16, dtype=torch.uint8, device=d_pb.device)
+        d_ko = _upload(32 * np.arange(n + 1, dtype=np.uint64), self.device)
+        torch.cuda.synchronize(d_pb.device)   # the library runs on its own stream
+        nat._check('pv_sha256_batch_device', self._lib.pv_sha256_batch_device(_dp(d_pb), _dp(d_po), n, -1, _dp(d_keys),
+                                                                            self.device, None))
+        try:
+            return _apply_unsorted_device(self._id, root_hash_of(root), n, d_keys, d_ko, d_vb, d_vo)[0]
         except nat.PlenumGpuError as exc:
             text = str(exc)
             if 'state apply: key ' in text:
