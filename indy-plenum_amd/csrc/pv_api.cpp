@@ -1000,10 +1000,6 @@ uint64_t small_bytes(const HostBatch& hb, uint64_t s, uint64_t e) {
   return (m + 1) * 8 + m * 96 + (hb.off[e] - hb.off[s]) + 16 + 16 + 8 * m;
 }
 
-// PV_ZC_POLL = 0 builds the stream-synchronize completion (A/B variant)
-#ifndef PV_ZC_POLL
-#define PV_ZC_POLL 1
-#endif
 // all-cached zero-copy calls up to this size complete by the keyed kernel's own
 // word: 64 signatures = the 16 blocks of 4 that profiles/r05_ab_completion_word.jsonl
 // measured faster than a k_signal launch (125 blocks measured slower)
@@ -1089,7 +1085,7 @@ int run_small(Device& d, const HostBatch& hb, uint64_t s, uint64_t e) {
   // polls (~5 us below a stream synchronize, tools/ubench/sync_lat.hip): an
   // all-cached call's keyed kernel writes it from its last block, other calls
   // end with a k_signal launch
-  const bool poll = zc && PV_ZC_POLL;
+  const bool poll = zc;
   uint32_t seq = 0;
   bool signalled = false;
   if (poll) {
@@ -2101,10 +2097,6 @@ int pv_sign_batch(const uint8_t* seeds, const uint8_t* msg_blob, const uint64_t*
 
 namespace {
 // leaf digests (n x 8 words) -> root (8 words) on stream s, all device memory
-// PV_MERKLE_TAIL_ON = 0: one k_merkle_level launch per level down to the root (A/B)
-#ifndef PV_MERKLE_TAIL_ON
-#define PV_MERKLE_TAIL_ON 1
-#endif
 // root of the empty tree: hash_empty(), SHA-256 of the empty string (ledger/tree_hasher.py:17-19)
 const uint32_t EMPTY_ROOT[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
                                 0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
@@ -2119,7 +2111,7 @@ int enqueue_merkle(Device& d, const uint8_t* blob, const uint64_t* off, uint64_t
   uint64_t m = n;
   int which = 0;
   while (m > 1) {
-    if (PV_MERKLE_TAIL_ON && m <= (uint64_t)pv::MERKLE_TAIL) {   // the last levels: one launch
+    if (m <= (uint64_t)pv::MERKLE_TAIL) {   // the last levels: one launch
       HIP_OK(pv::launch_merkle_tail(in, m, root, s));
       break;
     }

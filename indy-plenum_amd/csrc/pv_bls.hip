@@ -37,18 +37,13 @@ using namespace bn;
 constexpr int KEY_LINE_WORDS = N_LINES * LINE_WORDS;   // 2800 words per G2 point
 constexpr int MSG_WORDS = 4 * NL;                        // x_H, y_H, xq(-H), yq(-H)
 constexpr int BLS_BLOCK = 256;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PV_BN_MILLER_REGS)
+#if defined(__HIP_DEVICE_COMPILE__)
 static_assert(BLS_BLOCK == bn::MF_LANES && BLS_BLOCK == 2 * bn::MP_CHECKS,
               "the Miller loop's LDS accumulator is laid out per check block");
 #endif
 // the check kernel: one check per lane PAIR at 2 waves per SIMD
-// (k_bls_verify_pair, pv_bn254_pair.h); -DPV_BLS_ONE_LANE builds the one-lane
-// kernel k_bls_verify (512 registers, 1 wave per SIMD) for A/B timing
-#ifdef PV_BLS_ONE_LANE
-constexpr uint32_t BLS_WAVE_CHECKS = 64;   // checks per wave (= the key segments' padding)
-#else
-constexpr uint32_t BLS_WAVE_CHECKS = 32;
-#endif
+// (k_bls_verify_pair, pv_bn254_pair.h)
+constexpr uint32_t BLS_WAVE_CHECKS = 32;   // checks per wave (= the key segments' padding)
 // calls of at most pv_tuning.bls_quad_max checks (default PV_BLS_QUAD_MAX) run
 // one check per lane QUAD (k_bls_verify_quad: the two Miller loops on two lane
 // pairs, the final exponentiation's products split over both, 16 checks per
@@ -199,39 +194,6 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_bls_scatter(const uint32_t* __r
     if (key[e] < nkeys) order[lc[key[e]] + rank[e]] = (uint32_t)(base + (uint64_t)e * GROUP_BLOCK);
 }
 
-#ifdef PV_BLS_ONE_LANE
-// one lane per check, one key per wave (slots of `order` padded to 64 per key;
-// 0xffffffff = idle lane, which computes on the point at infinity and writes nothing)
-__global__ __launch_bounds__(BLS_BLOCK, 1) void k_bls_verify(
-    const uint8_t* __restrict__ sig, const uint32_t* __restrict__ msg_idx, const uint32_t* __restrict__ key_idx,
-    const uint32_t* __restrict__ order, const uint32_t* __restrict__ total, const uint32_t* __restrict__ msgtab,
-    const uint32_t* __restrict__ lines, const uint8_t* __restrict__ kstatus, uint32_t n_msgs,
-    uint8_t* __restrict__ verdict) {
-  const uint32_t slot = blockIdx.x * BLS_BLOCK + threadIdx.x;
-  const uint32_t task0 = __builtin_amdgcn_readfirstlane(slot & ~63u);
-  if (task0 >= *total) return;   // whole wave: past the last padded segment
-  const uint32_t j = order[slot];
-  const bool live = j != 0xffffffffu;
-  // lane 0 of a task is always live (segments fill from their start)
-  const uint32_t key = __builtin_amdgcn_readfirstlane(live ? key_idx[j] : 0u);
-  const uint32_t* g_lines = lines;
-  const uint32_t* pk_lines = lines + (uint64_t)KEY_LINE_WORDS * (1 + key);
-  const uint8_t st = kstatus[1 + key];
-  fp xs, ys, xqh = fzero(), yqh = fzero();
-  bool s_inf = true;
-  const bool msg_ok = live && msg_idx[j] < n_msgs;   // out of range: verdict 0
-  if (live) {
-    g1_decode(sig + 128ull * j, xs, ys, s_inf);
-    const uint32_t* t = msgtab + (uint64_t)MSG_WORDS * (msg_ok ? msg_idx[j] : 0u);
-    if (st == 0 && msg_ok) {
-      xqh = ld_fp(t + 2 * NL);
-      yqh = ld_fp(t + 3 * NL);
-    }
-  }
-  const bool ok = bls_check(xs, ys, s_inf, xqh, yqh, st == 1, g_lines, pk_lines);
-  if (live) verdict[j] = (st == 2 || !msg_ok) ? 0 : (uint8_t)ok;
-}
-#else
 // sigma's line point per check, one lane per check (the pair kernel would run
 // this chain -- decoding, one inversion -- on both lanes of a pair): word w of
 // check i at prep[w * n + i], w = 0..9 x/y, 10..19 1/y, 20 = 1 if sigma decodes
@@ -440,7 +402,6 @@ __global__ __launch_bounds__(BLS_BLOCK, 2) void k_bls_verify_oct(
   const bool ok = bls_check_oct_q(q, s_inf, st == 1, g_lines, pk_lines);
   if (live && (threadIdx.x & 7) == 0) verdict[j] = (st == 2 || !msg_ok) ? 0 : (uint8_t)ok;
 }
-#endif
 
 // Bls::verify_multi_sig's aggregated key (ursa: PointG2::new_inf() + every
 // ver_key.point): one lane per check sums its keys (each decoded as
@@ -664,13 +625,9 @@ int enqueue_verify(BlsDev& d, const KeySet& ks, const uint8_t* sig, const uint8_
   if (!ks.nkeys) return bfail(PV_ENOTINIT, "no BLS key set on device %d (call pv_bls_set_keys)", d.ord);
   if (n > 0x7fffffffull - 64ull * ks.nkeys) return bfail(PV_EINVAL, "too many checks in one call");
   if (n_msgs > 0xffffffffull) return bfail(PV_EINVAL, "too many messages in one call");
-#ifdef PV_BLS_ONE_LANE
-  const uint32_t pad = BLS_WAVE_CHECKS;
-#else
   const bool oct = n <= g_oct_max.load();
   const bool quad = !oct && n <= g_quad_max.load();
   const uint32_t pad = oct ? BLS_OCT_CHECKS : quad ? BLS_QUAD_CHECKS : BLS_WAVE_CHECKS;
-#endif
   const uint64_t slots = ((n + pad - 1) / pad + ks.nkeys) * pad;
   BLS_HIP(d.msgtab.ensure(n_msgs * MSG_WORDS));
   BLS_HIP(d.cnt.ensure(ks.nkeys));
@@ -678,18 +635,14 @@ int enqueue_verify(BlsDev& d, const KeySet& ks, const uint8_t* sig, const uint8_
   BLS_HIP(d.seg.ensure(ks.nkeys));
   BLS_HIP(d.total.ensure(1));
   BLS_HIP(d.order.ensure(slots));
-#ifndef PV_BLS_ONE_LANE
   BLS_HIP(d.sigprep.ensure(n * SIGPREP_WORDS));
-#endif
   BLS_HIP(hipEventRecord(d.ev[0], s));
-#ifndef PV_BLS_ONE_LANE
   if (quad || oct) {   // message hashing and sigma's prep in one launch (both timed as "hash")
     const uint32_t hb = blocks_for(8 * n_msgs, 64);
     if (n_msgs || n)
       hipLaunchKernelGGL(k_bls_prep, dim3(hb + blocks_for(n, 64)), dim3(64), 0, s, blob, off, (uint32_t)n_msgs, hb,
                          d.msgtab.p, sig, n, d.sigprep.p);
   } else
-#endif
   if (n_msgs) hipLaunchKernelGGL(k_bls_hash, dim3(blocks_for(n_msgs, 64)), dim3(64), 0, s, blob, off, (uint32_t)n_msgs,
                                  d.msgtab.p);
   BLS_HIP(hipGetLastError());
@@ -707,10 +660,6 @@ int enqueue_verify(BlsDev& d, const KeySet& ks, const uint8_t* sig, const uint8_
                      d.cursor.p, d.order.p);
   BLS_HIP(hipGetLastError());
   BLS_HIP(hipEventRecord(d.ev[2], s));
-#ifdef PV_BLS_ONE_LANE
-  hipLaunchKernelGGL(k_bls_verify, dim3(blocks_for(slots, BLS_BLOCK)), dim3(BLS_BLOCK), 0, s, sig, msg_idx, key_idx,
-                     d.order.p, d.total.p, d.msgtab.p, ks.lines.p, ks.kstatus.p, (uint32_t)n_msgs, verdict);
-#else
   if (n && !quad && !oct) hipLaunchKernelGGL(k_bls_sigprep, dim3(blocks_for(n, 64)), dim3(64), 0, s, sig, n, d.sigprep.p);
   if (oct)
     hipLaunchKernelGGL(k_bls_verify_oct, dim3(blocks_for(8 * slots, BLS_BLOCK)), dim3(BLS_BLOCK), 0, s, sig, msg_idx,
@@ -724,7 +673,6 @@ int enqueue_verify(BlsDev& d, const KeySet& ks, const uint8_t* sig, const uint8_
     hipLaunchKernelGGL(k_bls_verify_pair, dim3(blocks_for(2 * slots, BLS_BLOCK)), dim3(BLS_BLOCK), 0, s, sig, msg_idx,
                        key_idx, d.order.p, d.total.p, d.msgtab.p, ks.lines.p, ks.kstatus.p, (uint32_t)n_msgs,
                        d.sigprep.p, n, verdict);
-#endif
   BLS_HIP(hipGetLastError());
   BLS_HIP(hipEventRecord(d.ev[3], s));
   return PV_OK;

@@ -25,16 +25,6 @@
 #pragma once
 #include "pv_bn254.h"
 
-// the final exponentiation's Fp12-half operations (out of line by default)
-#ifndef PV_FE_CALL
-#define PV_FE_CALL PV_BN_CALL
-#endif
-#ifndef PV_FE_DCALL
-#define PV_FE_DCALL __device__ __noinline__
-#endif
-#ifndef PV_FE_F6MUL
-#define PV_FE_F6MUL f6mul
-#endif
 // member functions (PV_HD may be `static inline` in the host checker)
 #if defined(__HIPCC__)
 #define PV_MD __host__ __device__ __forceinline__
@@ -491,10 +481,10 @@ PV_HD p6 pr_mul_tail(const p6& t, const p2 (&m)[3]) {
   }
   return r;
 }
-PV_FE_CALL p6 pr_mul(const p6& x, const p6& y) {
+PV_BN_CALL p6 pr_mul(const p6& x, const p6& y) {
   p6 t;   // the out-of-line product first: nothing else is live across the call
 #pragma unroll
-  for (int j = 0; j < PL; ++j) t.e[j] = PV_FE_F6MUL(x.e[j], y.e[j]);
+  for (int j = 0; j < PL; ++j) t.e[j] = f6mul(x.e[j], y.e[j]);
   p2 m[3];
   {
     const p6 xo = pswap(x), yo = pswap(y);
@@ -518,17 +508,17 @@ PV_HD p6 pr_conj(const p6& x) {
 }
 // 1 / x = (a - b w) / (a^2 - v b^2): role 0 squares a, role 1 b; both invert
 // the same Fp6 norm
-PV_FE_CALL p6 pr_inv(const p6& x) {
+PV_BN_CALL p6 pr_inv(const p6& x) {
   p6 sq;
 #pragma unroll
-  for (int j = 0; j < PL; ++j) sq.e[j] = PV_FE_F6MUL(x.e[j], x.e[j]);
+  for (int j = 0; j < PL; ++j) sq.e[j] = f6mul(x.e[j], x.e[j]);
   const p6 so = pswap(sq);
   p6 r;
 #pragma unroll
   for (int j = 0; j < PL; ++j) {
     const int h = prole(j);
     const fp6 d = f6inv(f6sub(f6sel(h, so.e[j], sq.e[j]), f6mulv(f6sel(h, sq.e[j], so.e[j]))));
-    const fp6 m = PV_FE_F6MUL(x.e[j], d);
+    const fp6 m = f6mul(x.e[j], d);
     r.e[j] = f6sel(h, f6neg(m), m);
   }
   return r;
@@ -551,15 +541,15 @@ PV_HD p6 pr_frob_odd(const p6& x, int n, const uint32_t* const (&g)[10]) {
   (void)n;
   return r;
 }
-PV_FE_CALL p6 pr_frob1(const p6& x) {
+PV_BN_CALL p6 pr_frob1(const p6& x) {
   const uint32_t* const g[10] = {G1_1_A, G1_1_B, G1_2_A, G1_2_B, G1_3_A, G1_3_B, G1_4_A, G1_4_B, G1_5_A, G1_5_B};
   return pr_frob_odd(x, 1, g);
 }
-PV_FE_CALL p6 pr_frob3(const p6& x) {
+PV_BN_CALL p6 pr_frob3(const p6& x) {
   const uint32_t* const g[10] = {G3_1_A, G3_1_B, G3_2_A, G3_2_B, G3_3_A, G3_3_B, G3_4_A, G3_4_B, G3_5_A, G3_5_B};
   return pr_frob_odd(x, 3, g);
 }
-PV_FE_CALL p6 pr_frob2(const p6& x) {
+PV_BN_CALL p6 pr_frob2(const p6& x) {
   p6 r;
 #pragma unroll
   for (int j = 0; j < PL; ++j) {
@@ -598,7 +588,7 @@ PV_HD bool pr_is_one(const p6& x) {
 // Every sum is the pair version's (the same integers, so the same limbs).  The
 // host build has no quad: there pmul / pcyc / preduce / pinv are the pair ops.
 #if defined(__HIP_DEVICE_COMPILE__)
-PV_FE_DCALL p6 pr_mul_q(const p6& x, const p6& y) {
+__device__ __noinline__ p6 pr_mul_q(const p6& x, const p6& y) {
   const int h = prole(0);
   const bool g = qrole();
   p6 t;
@@ -618,7 +608,7 @@ PV_FE_DCALL p6 pr_mul_q(const p6& x, const p6& y) {
   return pr_mul_tail(t, m);
 }
 // pr_inv with its two Fp6 products split (the Fp6 inverse runs on both pairs)
-PV_FE_DCALL p6 pr_inv_q(const p6& x) {
+__device__ __noinline__ p6 pr_inv_q(const p6& x) {
   p6 sq;
   sq.e[0] = f6mul_q(x.e[0], x.e[0]);
   const p6 so = pswap(sq);
@@ -684,7 +674,7 @@ __device__ __forceinline__ void mq_reduce(pslot<ST> S) {
 // again between the two quads (orole g)
 // x y: of pair m's five products (its three of t, its m-product ma, and m2) quad
 // g = 0 forms t's first and second and m2, g = 1 t's third, ma and m2
-PV_FE_DCALL p6 pr_mul_o(const p6& x, const p6& y) {
+__device__ __noinline__ p6 pr_mul_o(const p6& x, const p6& y) {
   const int h = prole(0);
   const bool m = qrole(), g = orole();
   const fp6 &xs = x.e[0], &ys = y.e[0];
@@ -711,7 +701,7 @@ PV_FE_DCALL p6 pr_mul_o(const p6& x, const p6& y) {
   }
   return pr_mul_tail(t, mm);
 }
-PV_FE_DCALL p6 pr_inv_o(const p6& x) {
+__device__ __noinline__ p6 pr_inv_o(const p6& x) {
   p6 sq;
   sq.e[0] = f6mul_o4(x.e[0], x.e[0]);
   const p6 so = pswap(sq);
@@ -828,13 +818,6 @@ PV_BN_CALL p6 pr_cyc_sqr(pslot<ST> S, const p6& x) {
 // after every fourth: pr_pow_u's schedule); post = conjugation; then acc may be
 // parked.  The operands and their order are final_exp's (the chain below), and
 // every product forms pr_mul's sums, so every value has the same limbs.
-// PV_FE_PROG = 0 builds the chain of calls (A/B).
-#ifndef PV_FE_PROG
-#define PV_FE_PROG 1
-#endif
-#ifndef PV_FX_YHOLD
-#define PV_FX_YHOLD 0   // 1: the three Y = y + y' held through the m products (A/B)
-#endif
 constexpr uint32_t FX_MUL = 0, FX_INV = 1, FX_CYC = 2;
 constexpr uint32_t FX_ACC = 7, FX_NONE = 15;
 constexpr int FX_SLOTS = 5;   // 0 f (f0 before step 2), 1 f^u, 2 f^u^2, 3 t0, 4 t1
@@ -989,24 +972,12 @@ template <int ST>
 PV_HD void pr_mul_s(pslot<ST> S, const p6& y, bool conj) {
   p2 m[3];
   {
-#if PV_FX_YHOLD
-    p2 Y[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const p2 yk = p6c(y, k), yo = pswap(yk);
-#pragma unroll
-      for (int j = 0; j < PL; ++j) Y[k].e[j] = f2add(yk.e[j], yo.e[j]);
-    }
-    mp_fence();
-    auto Yk = [&](int k, int j) -> fp2 { return Y[k].e[j]; };
-#else
     // Y_k = y_k + y'_k formed where each product needs it (the partner's Fp2
     // crossing again): no three Y's held through the m products
     auto Yk = [&](int k, int j) -> fp2 {
       const p2 yk = p6c(y, k), yo = pswap(yk);
       return f2add(yk.e[j], yo.e[j]);
     };
-#endif
     // (a, b) of role 1's Karatsuba factor of m_k; role 0 takes X_k Y_k
     constexpr int KA[3] = {1, 0, 0}, KB[3] = {2, 1, 2};
 #pragma unroll
@@ -1162,11 +1133,8 @@ PV_HD p6 fx_get(pslot<ST> S, const p2 (&park)[3 * FX_SLOTS], uint32_t x, uint32_
 // final_exp(f0) on halves as FX_PROG: one loop, one copy of each operation.
 // Inlined into the pair kernel (one call site): as a call it saved and restored
 // the callee-saved VGPRs it uses on every check.
-#ifndef PV_FX_CALL
-#define PV_FX_CALL PV_HD
-#endif
 template <int ST>
-PV_FX_CALL p6 pr_final_exp_fx(pslot<ST> S, const p6& f0) {
+PV_HD p6 pr_final_exp_fx(pslot<ST> S, const p6& f0) {
   p2 park[3 * FX_SLOTS];
   fx_park_st(park, 0, f0);
   mp_put(S, f0);
@@ -1236,7 +1204,7 @@ PV_BN_CALL p6 pr_final_exp_chain(pslot<ST> S, const p6& f0) {
 // the pair kernel (LV 0) runs the step program, the quad / octet the chain
 template <int ST, int LV = 0>
 PV_HD p6 pr_final_exp(pslot<ST> S, const p6& f0) {
-  if constexpr (LV == 0 && PV_FE_PROG) return pr_final_exp_fx<ST>(S, f0);
+  if constexpr (LV == 0) return pr_final_exp_fx<ST>(S, f0);
   return pr_final_exp_chain<ST, LV>(S, f0);
 }
 

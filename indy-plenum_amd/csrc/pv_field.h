@@ -44,19 +44,6 @@
 #ifndef PV_CHECK_SQ2X
 #define PV_CHECK_SQ2X(f)
 #endif
-// Optional scheduling fence after every field multiply (-DPV_FE_FENCE_ON):
-// keeps the scheduler from interleaving consecutive multiplies.  Off by
-// default since the column-asm multiply (below): with each column one asm
-// block the interleaving is limited anyway, and the fence-free build measured
-// equal on C2 and 1-3 % faster on the keyed C3 curve
-// (profiles/r02_ab_colasm_c2.json, r02_ab_colasm_c3.json).
-#ifndef PV_FE_FENCE
-#if defined(__HIP_DEVICE_COMPILE__) && defined(PV_FE_FENCE_ON)
-#define PV_FE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define PV_FE_FENCE()
-#endif
-#endif
 
 namespace pv {
 
@@ -69,19 +56,10 @@ struct fe {
 
 PV_HD uint64_t mul32x32(uint32_t a, uint32_t b) { return (uint64_t)a * (uint64_t)b; }
 
-// 2x of a limb.  -DPV_TWICE_ADD forces v_add_u32 (asm) instead of the
-// compiler's v_lshlrev_b32: the isolated issue rates suggest it should be
-// cheaper (profiles/r01_int_cycles.json), but the doubling chain measured 2 %
-// slower with it (profiles/r02_fe_ilp_twice.txt), so the default is the shift.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PV_FE_NOASM) && defined(PV_TWICE_ADD)
-__device__ __forceinline__ uint32_t twice(uint32_t x) {
-  uint32_t y;
-  asm("v_add_u32 %0, %1, %1" : "=v"(y) : "v"(x));
-  return y;
-}
-#else
+// 2x of a limb: the compiler's v_lshlrev_b32.  A forced v_add_u32 (asm) should
+// be cheaper by the isolated issue rates (profiles/r01_int_cycles.json), but the
+// doubling chain measured 2 % slower with it (profiles/r02_fe_ilp_twice.txt).
 PV_HD uint32_t twice(uint32_t x) { return 2u * x; }
-#endif
 
 // Column sums as v_mad_u64_u32 chains whose first addend is the incoming
 // carry.  As plain C++ the compiler reassociates every column (starts it from
@@ -285,7 +263,6 @@ PV_HD void fe_mul(fe& h, const fe& f, const fe& g) {
     out[k] = (uint32_t)acc & ((k & 1) ? M25 : M26);
   }
   fe_finish_columns(h, carry, out);
-  PV_FE_FENCE();
 }
 
 // Squaring operands.  Product (i, j), i <= j, of MULT * f^2 carries the
@@ -380,7 +357,6 @@ PV_HD void fe_sq_t(fe& h, const fe& f) {
     out[k] = (uint32_t)acc & ((k & 1) ? M25 : M26);
   }
   fe_finish_columns(h, carry, out);
-  PV_FE_FENCE();
 }
 PV_HD void fe_sq(fe& h, const fe& f) {
   PV_COUNT(sq);
@@ -497,7 +473,6 @@ PV_HD void fe_mul2(fe& h0, const fe& f0, const fe& g0, fe& h1, const fe& f1, con
   const fe* const f[2] = {&f0, &f1};
   const fe* const g[2] = {&g0, &g1};
   fe_mul_n<2>(h, f, g);
-  PV_FE_FENCE();
 }
 PV_HD void fe_mul3(fe& h0, const fe& f0, const fe& g0, fe& h1, const fe& f1, const fe& g1, fe& h2, const fe& f2,
                    const fe& g2) {
@@ -508,7 +483,6 @@ PV_HD void fe_mul3(fe& h0, const fe& f0, const fe& g0, fe& h1, const fe& f1, con
   const fe* const f[3] = {&f0, &f1, &f2};
   const fe* const g[3] = {&g0, &g1, &g2};
   fe_mul_n<3>(h, f, g);
-  PV_FE_FENCE();
 }
 PV_HD void fe_sq2(fe& h0, const fe& f0, fe& h1, const fe& f1) {
   PV_CHECK_SQ(f0);
@@ -516,7 +490,6 @@ PV_HD void fe_sq2(fe& h0, const fe& f0, fe& h1, const fe& f1) {
   fe* const h[2] = {&h0, &h1};
   const fe* const f[2] = {&f0, &f1};
   fe_sq_n<2>(h, f);
-  PV_FE_FENCE();
 }
 
 // ---- latency forms (a wave alone on its SIMD: the latency kernels).
@@ -578,7 +551,6 @@ PV_HD void fe_mul_l(fe& h, const fe& f, const fe& g) {
     madc10x2z(col[k], col[k + 1], a[0], b[0], a[1], b[1]);
   }
   fe_carry_columns(h, col);
-  PV_FE_FENCE();
 }
 template <int MULT>
 PV_HD void fe_sq_lt(fe& h, const fe& f) {
@@ -596,7 +568,6 @@ PV_HD void fe_sq_lt(fe& h, const fe& f) {
   madc5x2z(col[5], col[7], as[5], bs[5], as[7], bs[7]);
   madc6_5z(col[8], col[9], as[8], bs[8], as[9], bs[9]);
   fe_carry_columns(h, col);
-  PV_FE_FENCE();
 }
 #endif
 PV_HD void fe_sq_l(fe& h, const fe& f) {
@@ -631,17 +602,14 @@ static constexpr uint32_t P2_E = 2u * ((1u << 26) - 1);
 static constexpr uint32_t P2_O = 2u * ((1u << 25) - 1);
 
 // One limb of a biased subtraction, f + K - g with K the 2p / 4p limb.
-// PV_SUB_SAD (default 1): on the device it is ONE v_sad_u32, |K - g| + f with K
+// On the device it is ONE v_sad_u32, |K - g| + f with K
 // in an SGPR (VOP3 takes no literal on gfx9), instead of the v_sub_u32 +
 // v_add_u32 pair the plain expression compiles to.  The two forms agree only
 // for g <= K, which is fe_sub's / fe_sub4's contract below (the host
 // bound-checking build asserts it at every call, PV_CHECK_SUB).  The asm is
 // forced because the compiler folds the plain |K - g| + f back into sub + add
-// wherever it can prove g <= K.  -DPV_SUB_SAD=0 builds the pair for A/B timing.
-#ifndef PV_SUB_SAD
-#define PV_SUB_SAD 1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PV_FE_NOASM) && PV_SUB_SAD
+// wherever it can prove g <= K.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PV_FE_NOASM)
 __device__ __forceinline__ uint32_t sub_bias(uint32_t K, uint32_t g, uint32_t f) {
   uint32_t r;
   asm("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "s"(K), "v"(g), "v"(f));

@@ -83,7 +83,7 @@ __device__ __forceinline__ uint64_t wave_append(unsigned long long* counter, uin
 // ever waits for an atomic round trip (k_hash refilled on nearly every trip on
 // C4 and waited for take_index's atomic each time).  Must be called with the
 // whole wavefront active (convergent code).
-// Chunk sizes (PV_HASH_GUIDED = 1) follow the batch's mean message length and
+// k_hash's chunk sizes (G = true) follow the batch's mean message length and
 // what is left.  A chunk holds about 16 x 64 blocks of work: 64 x max(1, 16 /
 // (mean blocks per message)) indices (mean from off[0], off[n]), so short
 // messages (C3: one SHA-512 block each -- at a fixed 64, one atomic per wave
@@ -97,15 +97,12 @@ __device__ __forceinline__ uint64_t wave_append(unsigned long long* counter, uin
 // what is left alone (up to 1024 from the start) gave C3 0.42, C2 0.43, f3's
 // leaf kernel 0.41 -> 0.38 ms, but C4 15.1 -> 16.3 ms (every wave streaming
 // its own far-apart MBs of a 17 GB blob); a trip-count estimate of the length
-// misjudged every wave's first chunk.  PV_HASH_GUIDED = 0: fixed chunks of
-// PV_HASH_CHUNK.  k_sha256 keeps fixed chunks (G = false): its f3 leaf kernel
+// misjudged every wave's first chunk.  k_sha256 keeps fixed chunks of
+// PV_HASH_CHUNK (G = false): its f3 leaf kernel
 // (5-block messages) measured 0.41 ms with them and 0.44-0.45 with the sized
 // ones (profiles/r06_ab_f3_queue.jsonl).
 #ifndef PV_HASH_CHUNK
 #define PV_HASH_CHUNK 64
-#endif
-#ifndef PV_HASH_GUIDED
-#define PV_HASH_GUIDED 1
 #endif
 struct WaveQueue {
   uint64_t cb;     // current chunk base
@@ -197,14 +194,6 @@ __device__ __forceinline__ uint64_t wave_task(unsigned long long* tasks) {
 #ifndef PV_HASH_WAVES
 #define PV_HASH_WAVES 2
 #endif
-#ifndef PV_HASH_LDS
-#define PV_HASH_LDS 0
-#endif
-// 16-byte groups of the next block's message window loaded one compression
-// ahead (0 = none)
-#ifndef PV_HASH_PF
-#define PV_HASH_PF 0
-#endif
 // libsodium's pre-checks on (R, S, A), one
 // lane per signature, ahead of the hash: keeps the branchy, load-dependent
 // check out of k_hash's refill path (which every ragged C4 iteration hit).
@@ -234,8 +223,8 @@ __global__ __launch_bounds__(HASH_BLOCK, PV_HASH_WAVES) void k_hash(const uint8_
   // prefetched next message: offsets, pre-check verdict, R || A
   WaveQueue q;
   // mean SHA-512 blocks per message from the blob's extent
-  wq_init<PV_HASH_GUIDED>(q, counter, n, PV_HASH_GUIDED ? wq_fit(n ? hram_blocks((off[n] - off[0]) / n) : 1) : 64);
-  uint64_t nidx = wq_take<PV_HASH_GUIDED>(q, true, counter), nmo = 0, nme = 0;
+  wq_init<true>(q, counter, n, wq_fit(n ? hram_blocks((off[n] - off[0]) / n) : 1));
+  uint64_t nidx = wq_take<true>(q, true, counter), nmo = 0, nme = 0;
   uint32_t nok = 0, nra[16];
   auto prefetch = [&]() {
     if (nidx < n) {
@@ -247,24 +236,6 @@ __global__ __launch_bounds__(HASH_BLOCK, PV_HASH_WAVES) void k_hash(const uint8_
     }
   };
   prefetch();
-#if PV_HASH_PF
-  // first groups of the next block's window (tagged by message offset + block)
-  uint32_t ypf[4 * PV_HASH_PF];
-  uint64_t pf_mo = ~0ull, pf_blk = 0;
-#endif
-#if PV_HASH_LDS
-  // Message blocks are staged through LDS by the whole wavefront: lane l's
-  // 144-byte window (9 groups of 16 B) is cut into 9 parts and part p is
-  // loaded by lane (9 l + p) % 64 in pass (9 l + p) / 64, so one load
-  // instruction of the wave covers ~7 consecutive windows (2 cache lines each)
-  // instead of 64 scattered ones (~4.5x fewer L1 tag lookups per block).
-  // Measured slower than per-lane loads (profiles/r02_ab_hash_queue.json):
-  // the kernel is not bound by the L1 tag rate.
-  constexpr int WB = 144;   // window bytes per lane
-  __shared__ uint4 win[HASH_BLOCK / 64][64 * WB / 16];
-  __shared__ uint4 desc[HASH_BLOCK / 64][64];
-  const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
-#endif
   // Convergent loop: every lane runs every trip (queue takes are wave-wide);
   // a lane without a block in progress idles through the compression.
   while (true) {
@@ -284,7 +255,7 @@ __global__ __launch_bounds__(HASH_BLOCK, PV_HASH_WAVES) void k_hash(const uint8_
         sha512_init(hs);
       }
     }
-    const uint64_t t = wq_take<PV_HASH_GUIDED>(q, promote, counter);
+    const uint64_t t = wq_take<true>(q, promote, counter);
     if (promote) {
       nidx = t;
       prefetch();
@@ -292,82 +263,10 @@ __global__ __launch_bounds__(HASH_BLOCK, PV_HASH_WAVES) void k_hash(const uint8_
     const bool active = blk < nblk;
     if (!__any(active || nidx < n)) break;   // nothing in progress, nothing queued
     uint64_t w[16];
-#if PV_HASH_LDS
-    {
-      // this lane's window: aligned-down start of block blk and the number of
-      // 16-byte groups holding message bytes (msg_fetch's rule)
-      const uint64_t qb = hram_q(blk);
-      const uint8_t* m = blob + mo;
-      const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(m) + qb) & 3u);
-      const int64_t rem = (int64_t)ml - (int64_t)qb;
-      int ng = 0;
-      if (active && rem + (int64_t)mis > 0) {
-        const int64_t g = (rem + (int64_t)mis + 15) / 16;
-        ng = (int)(g < (blk == 0 ? 5 : 9) ? g : (blk == 0 ? 5 : 9));
-      }
-      const uint64_t wa = reinterpret_cast<uint64_t>(m + qb - mis);
-      desc[wv][lane] = make_uint4((uint32_t)wa, (uint32_t)(wa >> 32), (uint32_t)ng, 0u);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const int gi = 64 * k + lane, owner = gi / 9, part = gi - 9 * (gi / 9);
-        const uint4 d = desc[wv][owner];
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (part < (int)d.z) {
-          const uint64_t a = ((uint64_t)d.y << 32 | d.x) + 16u * (uint32_t)part;
-          const uint32_t* p = reinterpret_cast<const uint32_t*>(a);
-          v = make_uint4(p[0], p[1], p[2], p[3]);
-        }
-        win[wv][gi] = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      uint32_t y[MSG_Y];
-#pragma unroll
-      for (int g = 0; g < 9; ++g) {
-        const uint4 v = win[wv][9 * lane + g];
-        y[4 * g] = v.x;
-        y[4 * g + 1] = v.y;
-        y[4 * g + 2] = v.z;
-        y[4 * g + 3] = v.w;
-      }
-      __builtin_amdgcn_wave_barrier();   // the next trip's stores come after these reads
-      if (active) hram_assemble_ra(w, y, ra, m, ml, blk, nblk);
-    }
-#endif
     if (active) {
-#if !PV_HASH_LDS
       uint32_t y[MSG_Y];
-#if PV_HASH_PF
-      // the window's first PV_HASH_PF groups were loaded during the previous
-      // compression when the tag matches; the rest now
-      if (pf_mo == mo && pf_blk == blk) {
-#pragma unroll
-        for (int k = 0; k < 4 * PV_HASH_PF; ++k) y[k] = ypf[k];
-        msg_fetch_part(y + 4 * PV_HASH_PF, blob + mo, ml, hram_q(blk), blk == 0, PV_HASH_PF, 9);
-      } else {
-        msg_fetch(y, blob + mo, ml, hram_q(blk), blk == 0);
-      }
-#else
       msg_fetch(y, blob + mo, ml, hram_q(blk), blk == 0);
-#endif
       hram_assemble_ra(w, y, ra, blob + mo, ml, blk, nblk);
-#if PV_HASH_PF
-      // next trip's block: blk + 1 of this message, or block 0 of the queued one
-      if (blk + 1 < nblk) {
-        pf_mo = mo;
-        pf_blk = blk + 1;
-        msg_fetch_part(ypf, blob + mo, ml, hram_q(blk + 1), false, 0, PV_HASH_PF);
-      } else if (nidx < n) {
-        pf_mo = nmo;
-        pf_blk = 0;
-        msg_fetch_part(ypf, blob + nmo, nme - nmo, 0, true, 0, PV_HASH_PF);
-      }
-#endif
-#endif
       sha512_compress(hs, w);
       if (++blk == nblk) {
         uint32_t d[16];
@@ -663,16 +562,6 @@ hipError_t launch_curve_lat(const uint8_t* pk, const uint8_t* sig, const uint32_
 #ifndef KQ_SMALL_MAX
 #define KQ_SMALL_MAX 256
 #endif
-// PV_QUAD_PHASE (timing variants only, wrong verdicts): 1 skips the hash +
-// lattice wave, 2 the decompressions + tables, 3 the windows
-#ifndef PV_QUAD_PHASE
-#define PV_QUAD_PHASE 0
-#endif
-// PV_QUAD_LDS_PAD (A/B variants only): extra LDS words per block, to cap the
-// blocks a CU holds
-#ifndef PV_QUAD_LDS_PAD
-#define PV_QUAD_LDS_PAD 0
-#endif
 // k_verify_quad: the whole verify of a small batch in ONE launch (latency
 // mode: pre-checks, SHA-512(R||A||M), the scalar stage and the lane-quad
 // curve stage).  A block of 128 threads takes 8 signatures: wave 1 (one lane
@@ -694,12 +583,11 @@ __global__ __launch_bounds__(128) void k_verify_quad(const uint8_t* __restrict__
                                                      uint8_t* __restrict__ verdict, uint8_t* __restrict__ bitmap_bytes,
                                                      uint64_t bitmap_len, unsigned long long* __restrict__ dcount,
                                                      int force_full) {
-  __shared__ uint32_t tabs[16 * QTAB_WORDS + PV_QUAD_LDS_PAD];
+  __shared__ uint32_t tabs[16 * QTAB_WORDS];
   __shared__ uint32_t recs[8 * HREC_WORDS];
   __shared__ uint64_t kws[SCHED ? 80 * 8 * KQ_SCHED_BLOCKS : 1];
   const int t = (int)threadIdx.x;
   const uint64_t i0 = (uint64_t)blockIdx.x * 8;
-  if (PV_QUAD_LDS_PAD && t == 0) tabs[16 * QTAB_WORDS] = 0;   // (keeps the padding allocated)
   const int side = (t >> 2) & 1;
   const QRole q = qrole_of((uint32_t)t & 3u);
   const uint64_t i = i0 + (uint64_t)((t & 63) >> 3);
@@ -713,7 +601,7 @@ __global__ __launch_bounds__(128) void k_verify_quad(const uint8_t* __restrict__
     if constexpr (SCHED) {
       const int sb = k & 7, bb = k >> 3;   // lane 8 b + s: block b's schedule of signature s
       const uint64_t js = i0 + (uint64_t)sb;
-      if (bb < KQ_SCHED_BLOCKS && js < n && PV_QUAD_PHASE != 1) {
+      if (bb < KQ_SCHED_BLOCKS && js < n) {
         const uint64_t ml = off[js + 1] - off[js];
         if ((uint64_t)bb < hram_blocks(ml))
           keyed_sched_block(kws + k, 8 * KQ_SCHED_BLOCKS, sig + 64 * js, pk + 32 * js, blob + off[js], ml,
@@ -726,7 +614,7 @@ __global__ __launch_bounds__(128) void k_verify_quad(const uint8_t* __restrict__
       uint32_t* r = recs + HREC_WORDS * k;
       r[HREC_FLAGS] = HS_NONE;
       const uint64_t j = i0 + (uint64_t)k;
-      if (j < n && PV_QUAD_PHASE != 1) {
+      if (j < n) {
         uint32_t dig[16];
         const uint64_t ml = off[j + 1] - off[j];
         const bool pre = SCHED ? keyed_hash(dig, kws + k, 8 * KQ_SCHED_BLOCKS, 8, sig + 64 * j, pk + 32 * j,
@@ -739,13 +627,13 @@ __global__ __launch_bounds__(128) void k_verify_quad(const uint8_t* __restrict__
     if (k == 0 && dm) atomicAdd(dcount, (unsigned long long)__popcll(dm));
   } else {
     // wave 0: the points and their tables
-    if (PV_QUAD_PHASE != 2) ok = q_side_table(Q, pk + 32 * ic, sig + 64 * ic, side, tabs + (t >> 2) * QTAB_WORDS, q);
+    ok = q_side_table(Q, pk + 32 * ic, sig + 64 * ic, side, tabs + (t >> 2) * QTAB_WORDS, q);
   }
   __syncthreads();
   if (t >= 64) return;
   const uint32_t* r = recs + HREC_WORDS * (t >> 3);
   const uint32_t st = r[HREC_FLAGS] & 0xffu;
-  if (PV_QUAD_PHASE != 3) q_side_msm(Q, r, side, tabs + (t >> 2) * QTAB_WORDS, side ? bw + 4 * BW_TABLE : bw, q);
+  q_side_msm(Q, r, side, tabs + (t >> 2) * QTAB_WORDS, side ? bw + 4 * BW_TABLE : bw, q);
   qfe e, e1;
   q_to_cached(e, Q, q);
 #pragma unroll
@@ -1027,11 +915,6 @@ constexpr int KQ_NR = 41;   // -R cached in add order (Y-X, Y+X, 2dT, 2Z) + deco
 constexpr int KQ_CW = 2;   // comb waves per block: 8 signatures x 4 sides, or 4 x 8 (small calls)
 constexpr int KQ_THREADS = 64 * (KQ_CW + 2);
 static_assert(KQ_SCHED_BLOCKS >= 1 && 8 * KQ_SCHED_BLOCKS <= 64, "one lane per (signature, block) of the hash wave");
-// PV_KEYED_PHASE (timing variants only, wrong verdicts), a bit mask: 1 skips the
-// -R square root (root wave), 2 the comb (comb waves), 4 the hash (hash wave)
-#ifndef PV_KEYED_PHASE
-#define PV_KEYED_PHASE 0
-#endif
 // a wave's LDS writes done, then the flag (lane 0); the waiting waves spin on it.
 // Every wave of the block is resident (one block = four waves on four SIMDs), so a
 // waiting wave never holds up the one it waits for.
@@ -1091,7 +974,7 @@ __global__ __launch_bounds__(KQ_THREADS) void k_verify_quad_keyed(const uint8_t*
     // those blocks (round 5: the hash -> comb path is the kernel's critical path)
     const int sb = k % SIG, bb = k / SIG;   // this lane's signature and block
     const uint64_t es = e0 + (uint64_t)sb;
-    const bool serve_s = !(PV_KEYED_PHASE & 4) && bb < KQ_SCHED_BLOCKS && es < n;
+    const bool serve_s = bb < KQ_SCHED_BLOCKS && es < n;
     uint64_t js = 0;
     if (serve_s) js = LIST ? list[es] : es;
     const uint8_t* as = pk + 32 * (pk_by_key ? (uint64_t)kidx[js] : js);
@@ -1104,8 +987,7 @@ __global__ __launch_bounds__(KQ_THREADS) void k_verify_quad_keyed(const uint8_t*
     if (k < SIG) {
       uint32_t dig[16];
       bool pre = false;
-      if (serve && !(PV_KEYED_PHASE & 4))
-        pre = keyed_hash(dig, kws + k, KSL, SIG, sig + 64 * j, as, blob + off[j], mlen_s);
+      if (serve) pre = keyed_hash(dig, kws + k, KSL, SIG, sig + 64 * j, as, blob + off[j], mlen_s);
       keyed_record(recs + KQ_WORDS * k, pre, dig);
     }
     kq_signal(ready);
@@ -1114,7 +996,7 @@ __global__ __launch_bounds__(KQ_THREADS) void k_verify_quad_keyed(const uint8_t*
       uint32_t* o = negr + KQ_NR * k;
       bool ok = false;
       ge_p3 P;
-      if (serve && !(PV_KEYED_PHASE & 1)) {
+      if (serve) {
         uint32_t enc[8];
         load8(enc, sig + 64 * j);
         ok = ge_frombytes_negate(P, enc) && y_is_canonical(enc);
@@ -1137,11 +1019,11 @@ __global__ __launch_bounds__(KQ_THREADS) void k_verify_quad_keyed(const uint8_t*
     const uint64_t ec = e < n ? e : n - 1;   // lanes past the batch run on the last signature (results dropped)
     const uint64_t ic = LIST ? list[ec] : ec;
     qfe acc, e_hi, e_lo;
-    if (!(PV_KEYED_PHASE & 2)) q_comb_base<SIDES>(e_hi, e_lo, sig + 64 * ic, side, bw, q);   // S B: no hash needed
+    q_comb_base<SIDES>(e_hi, e_lo, sig + 64 * ic, side, bw, q);   // S B: no hash needed
     const uint32_t* kt = ktab + (uint64_t)kidx[ic] * KEY_WORDS;
     const uint32_t* r = recs + KQ_WORDS * cs;
     kq_wait(ready);
-    if (!(PV_KEYED_PHASE & 2)) q_comb_side<SIDES>(acc, r, side, kt, e_hi, e_lo, q);
+    q_comb_side<SIDES>(acc, r, side, kt, e_hi, e_lo, q);
     // the sides' sum before -R is needed: side s + 1 -> s for even s (xor 4), then
     // side 2 -> 0 (xor 8) ..., so that only one add-and-test follows the root
     // wave's flag (round 5: the root chain is the longer path)
@@ -1339,11 +1221,6 @@ hipError_t launch_tally_bits(const uint32_t* bits, const uint32_t* dup, uint64_t
 }
 
 // ----------------------------------------------- SHA-256 / Merkle (row f3)
-// PV_SHA256_PREFETCH = 1: each lane's next block window is loaded during the
-// current compression (one trip ahead) instead of right before it
-#ifndef PV_SHA256_PREFETCH
-#define PV_SHA256_PREFETCH 1
-#endif
 // Batch SHA-256 of (prefix || M_i): persistent lanes with per-lane refill, the
 // same work-queue scheme as k_hash (ragged messages cost no divergence;
 // wave-private index chunks, next message's offsets loaded one message ahead).
@@ -1359,10 +1236,8 @@ __global__ __launch_bounds__(256) void k_sha256(const uint8_t* __restrict__ blob
     nme = off[nidx + 1];
   }
   uint32_t hs[8];
-#if PV_SHA256_PREFETCH
   uint32_t y[SHA256_Y];   // the window of the block this lane compresses next
   if (nidx < n) sha256_window(y, blob + nmo, nme - nmo, plen, 0);
-#endif
   while (true) {
     const bool promote = blk == nblk && nidx < n;
     if (promote) {
@@ -1385,15 +1260,11 @@ __global__ __launch_bounds__(256) void k_sha256(const uint8_t* __restrict__ blob
     if (!__any(active)) break;   // every message promotes on the trip it is taken
     if (active) {
       uint32_t w[16];
-#if PV_SHA256_PREFETCH
       sha256_assemble(w, y, blob + mo, ml, plen, prefix, blk, nblk);
       // the next trip's window in flight during this compression: block blk + 1,
       // or block 0 of the queued message (whose offsets are already loaded)
       if (blk + 1 < nblk) sha256_window(y, blob + mo, ml, plen, blk + 1);
       else if (nidx < n) sha256_window(y, blob + nmo, nme - nmo, plen, 0);
-#else
-      sha256_block(w, blob + mo, ml, plen, prefix, blk, nblk);
-#endif
       sha256_compress(hs, w);
       if (++blk == nblk) {
         uint32_t* o = out + 8 * idx;

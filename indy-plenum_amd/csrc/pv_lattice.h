@@ -283,13 +283,13 @@ PV_HD bool hs_euclid_classic(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], 
   return true;
 }
 
-// ---- the same reduction by Lehmer rounds (PV_LATTICE_LEHMER, default 1) ----
+// ---- the same reduction by Lehmer rounds (what half_scalars runs) ----
 // A round runs Euclid on the leading 53 bits of (ra, rb) only, collects the
 // quotients it can PROVE equal to the full-width ones in a 2x2 cofactor matrix
 // of magnitudes below 2^27, and applies the matrix to the long operands once.  The
 // partial quotients, the exit (first r_i < 2^128, always reached by an exact
-// full-width step) and hence every output word are those of hs_euclid_classic;
-// -DPV_LATTICE_LEHMER=0 builds the classical loop for A/B timing.
+// full-width step) and hence every output word are those of hs_euclid_classic,
+// which stays as the host tests' reference (half_scalars_classic below).
 //
 // With ra = xa 2^s + ea, rb = xb 2^s + eb (0 <= ea, eb < 2^s) and the cofactor
 // magnitudes u_j, v_j (u_{-1} = 1, v_{-1} = 0, u_0 = 0, v_0 = 1,
@@ -301,9 +301,6 @@ PV_HD bool hs_euclid_classic(uint32_t ra[8], uint32_t ta[HS_T], uint32_t rb[8], 
 //     x_{j+1} >= v_{j+1}   and   x_j - x_{j+1} >= v_{j+1} + v_j.
 // The first is strengthened to x_{j+1} >= v_{j+1} + T, T = ceil(2^128 / 2^s),
 // which proves r_{j+1} >= 2^128: a round never steps to or past the exit.
-#ifndef PV_LATTICE_LEHMER
-#define PV_LATTICE_LEHMER 1
-#endif
 constexpr int HS_MAX_STEPS = 192;   // the classical loop's 96 trips of two steps
 constexpr double HS_COF_CAP = 134217728.0;   // cofactors below 2^27: half the 53-bit window and a bit
 constexpr int HS_MAX_INNER = 48;    // v_j >= Fibonacci(j + 1), which passes 2^27 at j = 40
@@ -546,17 +543,13 @@ PV_HD uint32_t half_scalars(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_
   uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
   hs_init(ra, ta, rb, tb, h);
   uint32_t odd = 1;
-#if PV_LATTICE_LEHMER
   if (!hs_euclid_lehmer(ra, ta, rb, tb, odd)) return HS_DEFER;
-#else
-  if (!hs_euclid_classic(ra, ta, rb, tb, odd)) return HS_DEFER;
-#endif
   return hs_select(c, d, c_neg, ra, ta, rb, tb, odd);
 }
 
 #if !defined(__HIPCC__)
-// host builds only: the classical loop whatever the switch says (the tests'
-// reference), and the Lehmer rounds with their statistics
+// host builds only: the classical loop (the tests' reference), and the Lehmer
+// rounds with their statistics
 inline uint32_t half_scalars_classic(uint32_t c[HS_WORDS], uint32_t d[HS_WORDS], bool& c_neg, const uint32_t h[8]) {
   uint32_t ra[8], rb[8], ta[HS_T], tb[HS_T];
   hs_init(ra, ta, rb, tb, h);

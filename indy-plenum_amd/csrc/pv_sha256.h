@@ -92,17 +92,13 @@ PV_HD uint64_t sha256_blocks(uint64_t mlen, uint32_t plen) { return (plen + mlen
 
 // block `blk` of (prefix || M) as 16 big-endian words, SHA padding and length
 // applied, from the aligned-word window of its first data byte.
-// PV_SHA256_GROUPS = 1: the window is fetched as 4-word groups (group g is
+// The window is fetched as 4-word groups (group g is
 // loaded iff its first word holds a message byte: at most 5 dwordx4 loads per
 // lane and block instead of 17 guarded dword loads, each of which touches one
 // cache line per lane; a group reads at most 15 bytes past the message end, so
 // the blob needs >= 16 readable bytes after the last message), and the padding
 // is branch-free 32-bit selects (the clamped terminator position, as
-// msg_assemble of pv_verify_core.h); 0 = the per-word form (A/B baseline).
-#ifndef PV_SHA256_GROUPS
-#define PV_SHA256_GROUPS 1
-#endif
-#if PV_SHA256_GROUPS
+// msg_assemble of pv_verify_core.h).
 constexpr int SHA256_Y = 20;
 PV_HD void sha256_window(uint32_t y[SHA256_Y], const uint8_t* m, uint64_t mlen, uint32_t plen, uint64_t blk) {
   const bool pre = plen != 0 && blk == 0;
@@ -158,53 +154,6 @@ PV_HD void sha256_assemble(uint32_t w[16], const uint32_t y[SHA256_Y], const uin
     w[15] = (uint32_t)bits;
   }
 }
-#else
-constexpr int SHA256_Y = 17;
-// the aligned-word window of block blk of (prefix || M): 17 words from the
-// aligned-down first data byte, zero past the message (no load issued there)
-PV_HD void sha256_window(uint32_t y[SHA256_Y], const uint8_t* m, uint64_t mlen, uint32_t plen, uint64_t blk) {
-  const bool pre = plen != 0 && blk == 0;
-  const uint64_t q = pre ? 0 : 64 * blk - plen;        // first data byte of the window
-  const int64_t rem = (int64_t)mlen - (int64_t)q;
-  const uintptr_t base = reinterpret_cast<uintptr_t>(m) + q;
-  const uint32_t mis = (uint32_t)(base & 3u);
-  const uint32_t* wp = reinterpret_cast<const uint32_t*>(base - mis);
-#pragma unroll
-  for (int k = 0; k < 17; ++k) y[k] = (int64_t)(4 * k) - (int64_t)mis < rem ? wp[k] : 0u;
-}
-// block blk's 16 big-endian words from its window: funnel shift by the
-// misalignment, the prefix byte, the 0x80 terminator and the bit length
-PV_HD void sha256_assemble(uint32_t w[16], const uint32_t y[SHA256_Y], const uint8_t* m, uint64_t mlen, uint32_t plen,
-                           uint32_t prefix, uint64_t blk, uint64_t nblk) {
-  const bool pre = plen != 0 && blk == 0;
-  const uint64_t q = pre ? 0 : 64 * blk - plen;
-  const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(m) + q) & 3u);
-  uint32_t d[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) d[k] = funnel32_(y[k + 1], y[k], 8u * mis);
-  if (pre) {  // shift the data one byte up and put the prefix in byte 0
-#pragma unroll
-    for (int k = 15; k > 0; --k) d[k] = (d[k] << 8) | (d[k - 1] >> 24);
-    d[0] = (d[0] << 8) | (prefix & 0xffu);
-  }
-  const int64_t t = (int64_t)(plen + mlen) - (int64_t)(64 * blk);   // terminator position in this block
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int64_t r = t - 4 * k;
-    uint32_t v = d[k];
-    if (r < 4) {
-      const uint32_t keep = r <= 0 ? 0u : (1u << (8 * (uint32_t)r)) - 1u;
-      v = (v & keep) | ((r >= 0) ? (0x80u << (8 * (uint32_t)r)) : 0u);
-    }
-    w[k] = bswap32_(v);
-  }
-  if (blk + 1 == nblk) {
-    const uint64_t bits = (plen + mlen) * 8;
-    w[14] = (uint32_t)(bits >> 32);
-    w[15] = (uint32_t)bits;
-  }
-}
-#endif
 PV_HD void sha256_block(uint32_t w[16], const uint8_t* m, uint64_t mlen, uint32_t plen, uint32_t prefix, uint64_t blk,
                         uint64_t nblk) {
   uint32_t y[SHA256_Y];

@@ -9,10 +9,6 @@
 #include <stdint.h>
 #include "pv_field.h"
 
-#ifndef PV_SHA_ASM_ADD
-#define PV_SHA_ASM_ADD 1
-#endif
-
 namespace pv {
 
 // first 64 bits of the fractional parts of the cube roots of the first 80
@@ -124,7 +120,7 @@ PV_HD uint64_t maj64(uint64_t a, uint64_t b, uint64_t c) { return (a & b) | (a &
 // the compiler into a zero-extended low add plus a 32-bit high add and moves
 // of a zero register (3 extra instructions per round).
 PV_HD uint64_t add64(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__) && PV_SHA_ASM_ADD
+#if defined(__HIP_DEVICE_COMPILE__)
   uint64_t r;
   asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;

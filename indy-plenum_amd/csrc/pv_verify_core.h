@@ -18,9 +18,6 @@ namespace pv {
 
 constexpr int BT_ENTRIES = 129;   // niels k*B, k = 0..128
 constexpr int BT_WORDS = 32;      // 3 fe (30 words) padded to 32
-#ifndef PV_HALF_PREFETCH
-#define PV_HALF_PREFETCH 1
-#endif
 constexpr int AT_ENTRY = 40;      // cached entry words
 constexpr int AT_WORDS = 9 * 40;  // k*(-A), k = 0..8
 
@@ -127,7 +124,6 @@ PV_HD uint64_t hram_q(uint64_t blk) { return blk == 0 ? 0 : 128 * blk - 64; }
 // loads instead of 33 guarded dword loads.  Block 0 only needs words 0..16
 // (M[0, 64) behind R || A).  Words past the message are masked by
 // msg_assemble.  The pointer keeps the blob's address space (global loads).
-#ifndef PV_FETCH_WORDS
 constexpr int MSG_Y = 36;
 PV_HD void msg_fetch(uint32_t y[MSG_Y], const uint8_t* m, uint64_t mlen, uint64_t q, bool first) {
   const int64_t rem = (int64_t)mlen - (int64_t)q;
@@ -149,18 +145,6 @@ PV_HD void msg_fetch(uint32_t y[MSG_Y], const uint8_t* m, uint64_t mlen, uint64_
     y[4 * g + 3] = d;
   }
 }
-#else
-// (A/B baseline) one guarded dword load per word that holds a message byte
-constexpr int MSG_Y = 33;
-PV_HD void msg_fetch(uint32_t y[MSG_Y], const uint8_t* m, uint64_t mlen, uint64_t q, bool) {
-  const int64_t rem = (int64_t)mlen - (int64_t)q;
-  const uintptr_t base = reinterpret_cast<uintptr_t>(m) + q;
-  const uint32_t mis = (uint32_t)(base & 3u);
-  const uint32_t* wp = reinterpret_cast<const uint32_t*>(base - mis);
-#pragma unroll
-  for (int k = 0; k < 33; ++k) y[k] = (int64_t)(4 * k) - (int64_t)mis < rem ? wp[k] : 0u;
-}
-#endif
 
 // 32 little-endian words = message bytes [q, q + 128) with SHA padding applied:
 // bytes past mlen are zero and byte mlen is 0x80 (funnel shift of the raw words)
@@ -173,32 +157,6 @@ PV_HD uint32_t bitsel(uint32_t m, uint32_t a, uint32_t b) {
   return (a & m) | (b & ~m);
 #endif
 }
-
-#ifndef PV_FETCH_WORDS
-// groups [g0, g1) of msg_fetch's window only (the same guards): k_hash loads
-// the window's first groups one compression ahead (PV_HASH_PF)
-PV_HD void msg_fetch_part(uint32_t* y, const uint8_t* m, uint64_t mlen, uint64_t q, bool first, int g0, int g1) {
-  const int64_t rem = (int64_t)mlen - (int64_t)q;
-  const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(m) + q) & 3u);
-  const uint32_t* wp = reinterpret_cast<const uint32_t*>(m + q - mis);
-#pragma unroll
-  for (int g = 0; g < 9; ++g) {
-    if (g < g0 || g >= g1) continue;
-    const bool ld = (int64_t)(16 * g) - (int64_t)mis < rem && (!first || g < 5);
-    uint32_t a = 0, b = 0, c = 0, d = 0;
-    if (ld) {
-      a = wp[4 * g];
-      b = wp[4 * g + 1];
-      c = wp[4 * g + 2];
-      d = wp[4 * g + 3];
-    }
-    y[4 * (g - g0)] = a;
-    y[4 * (g - g0) + 1] = b;
-    y[4 * (g - g0) + 2] = c;
-    y[4 * (g - g0) + 3] = d;
-  }
-}
-#endif
 
 PV_HD void msg_assemble(uint32_t x[32], const uint32_t y[MSG_Y], const uint8_t* m, uint64_t mlen, uint64_t q) {
   const int64_t rem64 = (int64_t)mlen - (int64_t)q;
@@ -427,24 +385,12 @@ PV_HD void load_entry(ge_entry& e, const uint32_t* q, bool neg) {
 // same operation sequence (and operand bounds) as ge_add_cached_at
 PV_HD void ge_add_entry(ge_p1p1& r, const ge_p3& p, const ge_entry& e, bool neg) {
   fe c, d, a, b, u, v;
-#if PV_FUSE & 4
-  fe_mul2(c, e.t2d, p.T, d, p.Z, e.z2);
-  fe_add(u, p.Y, p.X);
-  fe_sub(v, p.Y, p.X);
-#if PV_FUSE & 4
-  fe_mul2(a, u, e.a, b, v, e.b);
-#else
-  fe_mul(a, u, e.a);
-  fe_mul(b, v, e.b);
-#endif
-#else
   fe_mul(c, e.t2d, p.T);
   fe_mul(d, p.Z, e.z2);
   fe_add(u, p.Y, p.X);
   fe_mul(a, u, e.a);
   fe_sub(v, p.Y, p.X);
   fe_mul(b, v, e.b);
-#endif
   fe_sub(r.X, a, b);
   fe_add(r.Y, a, b);
   fe_neg(u, c);
@@ -470,12 +416,8 @@ PV_HD void ge_madd_entry(ge_p1p1& r, const ge_p3& p, const ge_nentry& e, bool ne
   fe_carry(d);
   fe_add(u, p.Y, p.X);
   fe_sub(v, p.Y, p.X);
-#if PV_FUSE & 4
-  fe_mul2(a, u, e.a, b, v, e.b);
-#else
   fe_mul(a, u, e.a);
   fe_mul(b, v, e.b);
-#endif
   fe_sub(r.X, a, b);
   fe_add(r.Y, a, b);
   fe_neg(u, c);
@@ -623,10 +565,6 @@ constexpr int KEY_WORDS = KEY_STATUS + 32;   // status word + padding: every key
 // so k_keys lays it out lane-interleaved ([word][lane] per 64 keys: every
 // scratch load and store of a wave is one contiguous 256-byte row); only the
 // final affine entries go to the key-major table the curve kernel reads.
-// PV_KEYS_XYP = 1 (A/B): the prefix products folded into X and Y, see key_prepare
-#ifndef PV_KEYS_XYP
-#define PV_KEYS_XYP 0
-#endif
 constexpr int KS_XYZ = 0;
 constexpr int KS_PREFIX = 8 * COMB_Q * 30;
 constexpr int KEY_SCRATCH = KS_PREFIX + 8 * COMB_Q * 10;
@@ -682,33 +620,6 @@ PV_HD void key_prepare(uint32_t* kt, uint32_t* scr, const uint8_t* pk) {
     ge_cached c1;
     ge_p3_to_cached(c1, P);
     ge_p3 Q = P;
-#if PV_KEYS_XYP
-    // (A/B) X P_(e-1), Y P_(e-1), Z per entry: 30 scratch words instead of
-    // 40, one more multiply per entry (backward: x = X' acc, y = Y' acc)
-    auto put = [&](int e, const ge_p3& R) {
-      if (e == 0) {
-        store_fe<LS>(xyz(e), R.X);
-        store_fe<LS>(xyz(e) + 10 * LS, R.Y);
-        fe_copy(zacc, R.Z);
-      } else {
-        fe t;
-        fe_mul(t, R.X, zacc);
-        store_fe<LS>(xyz(e), t);
-        fe_mul(t, R.Y, zacc);
-        store_fe<LS>(xyz(e) + 10 * LS, t);
-        fe_mul(zacc, zacc, R.Z);
-      }
-      store_fe<LS>(xyz(e) + 20 * LS, R.Z);
-    };
-    put(8 * q, Q);
-#pragma unroll 1
-    for (int k = 2; k <= 8; ++k) {
-      ge_p1p1 t;
-      ge_add_cached(t, Q, c1, false);
-      ge_p1p1_to_p3(Q, t);
-      put(8 * q + k - 1, Q);
-    }
-#else
     store_fe<LS>(xyz(8 * q), Q.X);
     store_fe<LS>(xyz(8 * q) + 10 * LS, Q.Y);
     store_fe<LS>(xyz(8 * q) + 20 * LS, Q.Z);
@@ -729,7 +640,6 @@ PV_HD void key_prepare(uint32_t* kt, uint32_t* scr, const uint8_t* pk) {
       fe_mul(zacc, zacc, Q.Z);
       store_fe<LS>(pre(e), zacc);
     }
-#endif
     if (q + 1 < COMB_Q) {  // A_{q+1} = 2^32 A_q = 2^29 (8 A_q)
       ge_p1p1 t;
       ge_p2 r;
@@ -753,9 +663,7 @@ PV_HD void key_prepare(uint32_t* kt, uint32_t* scr, const uint8_t* pk) {
   fe_invert(acc, zacc);
   fe d2;
   fe_const_d2(d2);
-#if !PV_KEYS_XYP
   load_fe<LS>(un, pre(NE - 2));
-#endif
   load_fe<LS>(xn, xyz(NE - 1));
   load_fe<LS>(yn, xyz(NE - 1) + 10 * LS);
   load_fe<LS>(zn, xyz(NE - 1) + 20 * LS);
@@ -767,19 +675,11 @@ PV_HD void key_prepare(uint32_t* kt, uint32_t* scr, const uint8_t* pk) {
     fe_copy(x, xn);
     fe_copy(y, yn);
     if (e > 0) {
-#if !PV_KEYS_XYP
       if (e > 1) load_fe<LS>(un, pre(e - 2));
-#endif
       load_fe<LS>(xn, xyz(e - 1));
       load_fe<LS>(yn, xyz(e - 1) + 10 * LS);
       load_fe<LS>(zn, xyz(e - 1) + 20 * LS);
     }
-#if PV_KEYS_XYP
-    // acc = (Z_0 ... Z_e)^-1 and X' = X P_(e-1): x = X' acc = X / Z_e
-    fe_mul(x, x, acc);
-    fe_mul(y, y, acc);
-    if (e > 0) fe_mul(acc, acc, z);  // (Z_0 ... Z_{e-1})^-1
-#else
     fe zi;
     if (e > 0) {
       fe_mul(zi, acc, u);            // Z_e^-1
@@ -789,7 +689,6 @@ PV_HD void key_prepare(uint32_t* kt, uint32_t* scr, const uint8_t* pk) {
     }
     fe_mul(x, x, zi);
     fe_mul(y, y, zi);
-#endif
     fe ypx, ymx;
     fe_add(ypx, y, x); fe_carry(ypx);
     fe_sub(ymx, y, x); fe_carry(ymx);
@@ -1314,13 +1213,11 @@ PV_HD void msm_half(ge_p1p1& t, const uint32_t* rec, const uint32_t* atab, const
     ge_add_cached_at<LS>(t, acc, rtab + (dR < 0 ? -dR : dR) * AT_ENTRY * LS, dR < 0);
     ge_p1p1_to_p2(r2, t);
   }
-#if PV_HALF_PREFETCH
   // software pipeline: the +-A entry of window w is loaded before its four
   // doublings, the -R entry before the +-A add
   ge_entry ea, er;
   int dA = (int)((cw >> 28) & 15u) - 8;
   load_entry<LS>(ea, atab + (dA < 0 ? -dA : dA) * AT_ENTRY * LS, dA < 0);
-#endif
 #pragma unroll 1
   for (int w = 31; w >= 0; --w) {
     if ((w & 7) == 7 && w != 31) {
@@ -1345,7 +1242,6 @@ PV_HD void msm_half(ge_p1p1& t, const uint32_t* rec, const uint32_t* atab, const
     ge_p2_dbl(t, r2);
     ge_p1p1_to_p3(acc, t);
     const int sh4 = 4 * (w & 7);
-#if PV_HALF_PREFETCH
     const int dR = (int)((dw >> sh4) & 15u) - 8;
     load_entry<LS>(er, rtab + (dR < 0 ? -dR : dR) * AT_ENTRY * LS, dR < 0);
     ge_add_entry(t, acc, ea, dA < 0);
@@ -1368,37 +1264,13 @@ PV_HD void msm_half(ge_p1p1& t, const uint32_t* rec, const uint32_t* atab, const
       ge_p1p1_to_p3(acc, t);
       ge_madd_entry(t, acc, ec, dH < 0);
     }
-#else
-    const int dA = (int)((cw >> sh4) & 15u) - 8;
-    ge_add_cached_at<LS>(t, acc, atab + (dA < 0 ? -dA : dA) * AT_ENTRY * LS, dA < 0);
-    ge_p1p1_to_p3(acc, t);
-    const int dR = (int)((dw >> sh4) & 15u) - 8;
-    ge_add_cached_at<LS>(t, acc, rtab + (dR < 0 ? -dR : dR) * AT_ENTRY * LS, dR < 0);
-    if ((w & 3) == 0) {
-      // base-point digits: 16-bit digit w / 4 of each half of s' (the
-      // entries come from L2/MALL: each load is issued one step ahead)
-      const int sh16 = 16 * ((w >> 2) & 1);
-      const int dL = (int)((lw >> sh16) & 0xffffu) - 32768;
-      const int dH = (int)((hw >> sh16) & 0xffffu) - 32768;
-      ge_nentry eb;
-      load_nentry(eb, blo + (dL < 0 ? -dL : dL) * BT_WORDS, dL < 0);
-      ge_p1p1_to_p3(acc, t);
-      ge_nentry ec;
-      load_nentry(ec, bhi + (dH < 0 ? -dH : dH) * BT_WORDS, dH < 0);
-      ge_madd_entry(t, acc, eb, dL < 0);
-      ge_p1p1_to_p3(acc, t);
-      ge_madd_entry(t, acc, ec, dH < 0);
-    }
-#endif
     if (w == 0) break;
-#if PV_HALF_PREFETCH
     {
       // digit of window w - 1: its word is the next group's when w - 1 starts one
       const uint32_t nw = ((w - 1) & 7) == 7 ? cn : cw;
       dA = (int)((nw >> (4 * ((w - 1) & 7))) & 15u) - 8;
       load_entry<LS>(ea, atab + (dA < 0 ? -dA : dA) * AT_ENTRY * LS, dA < 0);
     }
-#endif
     ge_p1p1_to_p2(r2, t);
   }
 }

@@ -5,9 +5,9 @@ the planted families of tests/_lattice_cases.py; the same as a restatement
 over Python integers; and once more as a program of its own under
 AddressSanitizer + UBSan.  Exact integers everywhere: there is no tolerance.
 
-hc_half_scalars is the form the build's PV_LATTICE_LEHMER selects;
-hc_half_scalars_lehmer and hc_half_scalars_classic are the two loops whatever
-the switch says, so the comparisons hold for both settings."""
+hc_half_scalars is the product's form (the Lehmer rounds); hc_half_scalars_lehmer
+and hc_half_scalars_classic name the two loops explicitly, the classical one being
+the reference."""
 import ctypes
 import os
 import struct

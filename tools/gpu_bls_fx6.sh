@@ -2,7 +2,9 @@
 # Round 6: the pair kernel's final exponentiation as a step
 # program whose product streams its first operand from the LDS slot.  GPU ==
 # oracle BLS tests, the c3bls line interleaved against the chain-of-calls build
-# (indy-plenum_amd/lib/ab_fe_chain.so: -D PV_FE_PROG=0), FETCH / WRITE passes.
+# (indy-plenum_amd/lib/ab_fe_chain.so: -D PV_FE_PROG=0, a switch of the tree at
+# that time, since retired), FETCH / WRITE passes (profiles/r06_bls_pmc.json,
+# which bench.py reads).
 #   bash tools/gpu_bls_fx6.sh OUT
 set -u
 out=${1:-gpurun_out/blsfx6}

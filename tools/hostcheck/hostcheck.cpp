@@ -243,7 +243,7 @@ uint32_t hc_half_scalars(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_
 }
 
 // the same through the classical one-step-at-a-time loop (the reference of the
-// Lehmer rounds, whatever PV_LATTICE_LEHMER says)
+// Lehmer rounds)
 uint32_t hc_half_scalars_classic(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_t* c_neg) {
   uint32_t h[8], c[HS_WORDS], d[HS_WORDS];
   memcpy(h, h32, 32);
@@ -255,7 +255,7 @@ uint32_t hc_half_scalars_classic(const uint8_t* h32, uint8_t* c20, uint8_t* d20,
   return st;
 }
 
-// the same through the Lehmer rounds, whatever PV_LATTICE_LEHMER says
+// the same through the Lehmer rounds, called by name
 uint32_t hc_half_scalars_lehmer(const uint8_t* h32, uint8_t* c20, uint8_t* d20, uint32_t* c_neg) {
   uint32_t h[8], c[HS_WORDS], d[HS_WORDS];
   memcpy(h, h32, 32);

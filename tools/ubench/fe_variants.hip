@@ -13,6 +13,11 @@
 
 using namespace pv;
 
+// variant A's scheduling fence after every field op (the product's field code
+// had it as an option until the fence-free build measured equal or faster,
+// profiles/r02_ab_colasm_c2.json, r02_ab_colasm_c3.json)
+#define FE_FENCE() __builtin_amdgcn_sched_barrier(0)
+
 // 64-bit accumulate of a 32x32 product as ONE v_mad_u64_u32 whose addend is
 // the running sum: the compiler cannot reassociate an asm statement, so the
 // column's carry stays the first addend instead of becoming a trailing
@@ -52,7 +57,7 @@ __device__ __forceinline__ void mul_a(fe& h, const fe& f, const fe& g) {
     out[k] = (uint32_t)acc & ((k & 1) ? M25 : M26);
   }
   fe_finish_columns(h, carry, out);
-  PV_FE_FENCE();
+  FE_FENCE();
 }
 
 __device__ __forceinline__ void sq_a(fe& h, const fe& f) {
@@ -92,7 +97,7 @@ __device__ __forceinline__ void sq_a(fe& h, const fe& f) {
     out[k] = (uint32_t)acc & ((k & 1) ? M25 : M26);
   }
   fe_finish_columns(h, carry, out);
-  PV_FE_FENCE();
+  FE_FENCE();
 }
 
 // ---- variant B: A without the per-op scheduling fence (the compiler may
