@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (pv_api.cpp) and the HIP
+// Internal launch interface between the C-ABI layer (pv_api*.cpp) and the HIP
 // kernels (pv_kernels.hip).  All pointers are device pointers on the current
 // device; every launch is asynchronous on `stream`.
 #pragma once

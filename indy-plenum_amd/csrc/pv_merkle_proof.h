@@ -26,7 +26,7 @@
 
 namespace pv {
 
-// == PV_MP_* of include/plenum_verify.h (pv_api.cpp asserts it)
+// == PV_MP_* of include/plenum_verify.h (pv_kernels.hip asserts it)
 constexpr uint32_t MP_OK = 0;
 constexpr uint32_t MP_BAD_RANGE = 1;      // index >= tree_size, old_size > new_size
 constexpr uint32_t MP_TOO_SHORT = 2;

@@ -247,7 +247,7 @@ class Tuning(ctypes.Structure):
 CURVE_MODES = {0: 'half', 1: 'full', 2: 'grouped'}   # PV_CURVE_HALF / _FULL / _GROUPED
 LAT_KERNELS = {'quad': 0, 'pair': 1}                 # PV_LAT_QUAD / PV_LAT_PAIR
 STAGING_MODES = {0: 'pinned', 1: 'pageable'}         # PV_STAGING_PINNED / _PAGEABLE
-LAT_MAX_DEFAULT = 32768                              # defaults of pv_tuning (csrc/pv_api.cpp)
+LAT_MAX_DEFAULT = 32768                              # defaults of pv_tuning (csrc/pv_api_common.h)
 LAT_KEYED_MAX_DEFAULT = 8192
 
 

@@ -74,7 +74,7 @@ def ctx():
     assert Ctx.lib.pv_merkle_tree_extend_hashes(h.value, leaves.ctypes.data, 3) == OK, Ctx.lib.pv_last_error()
     Ctx.tree = h.value
     yield Ctx
-    assert Ctx.lib.pv_merkle_tree_free(h.value) == OK
+    assert Ctx.lib.pv_merkle_tree_free(Ctx.tree) == OK   # the last test re-creates it after a pv_shutdown
 
 
 def call(ctx, name, over, all_null=False):
@@ -329,3 +329,65 @@ def test_tuning_rlp_and_timing(ctx):
                 ('pv_synth_fill_device', {'mode': 3}, EINVAL, 'unknown synth mode 3'),
                 ('pv_synth_fill_device', {'mode': 2, 'n_nodes': 1025}, EINVAL, 'n_nodes must be in 1..1024'),
                 ('pv_keycache_add', {'k': 0xffffffff}, EINVAL, 'key cache limited to 2^32 - 2 keys')])
+
+
+def test_freed_handles_are_refused_and_reused(ctx):
+    """Trees and stores created interleaved: a freed id is refused in the pinned words while its
+    neighbours keep their contents, the next create of that kind gets the freed id back (the
+    lowest free slot) with an empty object, and pv_shutdown + pv_init leaves no id behind."""
+    import hashlib
+    from plenum_gpu import _native
+    lib = ctx.lib
+    empty = hashlib.sha256(b'').digest()
+    leaves = np.arange(64, dtype=np.uint8)
+    node = np.frombuffer(b'\xc6\x85hello', np.uint8)
+
+    def tree_info(h):
+        n, depth, root = ctypes.c_uint64(77), ctypes.c_uint32(77), np.zeros(32, np.uint8)
+        rc = lib.pv_merkle_tree_info(h, ctypes.byref(n), ctypes.byref(depth), root.ctypes.data)
+        return (rc, lib.pv_last_error().decode()) if rc else (n.value, depth.value, root.tobytes())
+
+    def store_info(s):
+        v = [ctypes.c_uint64(77) for _ in range(4)]
+        rc = lib.pv_state_store_info(s, *[ctypes.byref(x) for x in v])
+        return (rc, lib.pv_last_error().decode()) if rc else tuple(x.value for x in v[:3])
+
+    def create():
+        h, s = ctypes.c_int32(0), ctypes.c_int32(0)
+        assert lib.pv_merkle_tree_create(1, 0, ctypes.byref(h)) == OK, lib.pv_last_error()
+        assert lib.pv_state_store_create(1, 1, 0, ctypes.byref(s)) == OK, lib.pv_last_error()
+        return h.value, s.value
+
+    def no_tree(h):
+        return EINVAL, 'no Merkle tree with handle {}'.format(h)
+
+    def no_store(s):
+        return EINVAL, 'no state store with id {}'.format(s)
+
+    try:
+        (t1, s1), (t2, s2), (t3, s3) = create(), create(), create()
+        assert t1 < t2 < t3 and s1 < s2 < s3
+        assert lib.pv_merkle_tree_extend_hashes(t2, leaves.ctypes.data, 2) == OK, lib.pv_last_error()
+        added = ctypes.c_uint64(0)
+        assert lib.pv_state_store_add(s2, node.ctypes.data, u64(0, node.size).ctypes.data, 1, None,
+                                      ctypes.byref(added)) == OK, lib.pv_last_error()
+        assert tree_info(t2) == (2, 1, hashlib.sha256(b'\x01' + leaves.tobytes()).digest())
+        assert added.value == 1 and store_info(s2) == (1, 1, node.size)
+        assert lib.pv_merkle_tree_free(t2) == OK and lib.pv_state_store_free(s2) == OK
+        assert tree_info(t2) == no_tree(t2) and store_info(s2) == no_store(s2)
+        for t, s in ((t1, s1), (t3, s3)):
+            assert tree_info(t) == (0, 0, empty) and store_info(s) == (0, 0, 0)
+        assert tree_info(ctx.tree)[:2] == (3, 2)
+        assert create() == (t2, s2)
+        assert tree_info(t2) == (0, 0, empty) and store_info(s2) == (0, 0, 0)
+        _native.shutdown()
+        _native.ensure_init()
+        for t, s in ((t1, s1), (t2, s2), (t3, s3)):
+            assert tree_info(t) == no_tree(t) and store_info(s) == no_store(s)
+        assert tree_info(ctx.tree) == no_tree(ctx.tree)
+    finally:   # the module's tree, for whatever runs after this test
+        _native.ensure_init()
+        h = ctypes.c_int32(0)
+        assert lib.pv_merkle_tree_create(4, 0, ctypes.byref(h)) == OK, lib.pv_last_error()
+        assert lib.pv_merkle_tree_extend_hashes(h.value, np.arange(96, dtype=np.uint8).ctypes.data, 3) == OK
+        ctx.tree = h.value

@@ -558,7 +558,7 @@ def test_generated_paths_and_proofs_verify_without_leaving_the_device(lib, resid
 # ------------------------------- 5. the second trip of the grid-stride kernels
 def second_trip_k():
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    cap = cus * 32 * 256            # merkle_blocks() of csrc/pv_api.cpp: 32 blocks of 256 per CU
+    cap = cus * 32 * 256            # merkle_blocks() of csrc/pv_api_common.h: 32 blocks of 256 per CU
     k = cap + 2 * 256 + 37
     assert k > cap, 'this test no longer reaches a second trip of the proof kernels'
     return k
