@@ -1826,8 +1826,8 @@ __global__ __launch_bounds__(256) void k_trie_proof_pack(
     const uint32_t count = node_count[q];
     uint64_t body;
     if (e <= o || !sg_pack_check(beg, end, n_nodes, ids, count, max_nodes, e - o, body)) continue;
-    const uint32_t hl = rlp_list_header_len(body);
-    if (lane < hl) out[o + lane] = rlp_list_header_byte(body, hl, lane);
+    const uint32_t hl = rlp_header_len(body);
+    if (lane < hl) out[o + lane] = rlp_header_byte(192, body, hl, lane);
     uint64_t w = o + hl;
     for (uint32_t k = count; k-- > 0;) {
       const uint32_t id = ids[k];

@@ -321,23 +321,16 @@ PV_HD uint32_t tb_struct_one(const TbCtx& c, uint64_t i) {
 }
 
 // ---------------------------------------------------------------- RLP pieces
-// byte k < hl of the header over `body` bytes; base 128: a string, 192: a list
-PV_HD uint8_t tb_hdr_byte(uint32_t base, uint64_t body, uint32_t hl, uint32_t k) {
-  if (hl == 1) return (uint8_t)(base + body);
-  if (k == 0) return (uint8_t)(base + 55 + (hl - 1));
-  return (uint8_t)(body >> (8 * (hl - 1 - k)));
-}
-
 PV_HD uint8_t* tb_put_hdr(uint8_t* w, uint32_t base, uint64_t body) {
-  const uint32_t hl = rlp_list_header_len(body);
-  for (uint32_t k = 0; k < hl && k < 9; ++k) *w++ = tb_hdr_byte(base, body, hl, k);
+  const uint32_t hl = rlp_header_len(body);
+  for (uint32_t k = 0; k < hl && k < 9; ++k) *w++ = rlp_header_byte(base, body, hl, k);
   return w;
 }
 
 // a byte string as an RLP item
 PV_HD uint64_t tb_str_len(const uint8_t* s, uint64_t len) {
   if (len == 1 && s[0] < 0x80) return 1;
-  return rlp_list_header_len(len) + len;
+  return rlp_header_len(len) + len;
 }
 
 PV_HD uint8_t* tb_put_str(uint8_t* w, const uint8_t* s, uint64_t len) {
@@ -349,7 +342,7 @@ PV_HD uint8_t* tb_put_str(uint8_t* w, const uint8_t* s, uint64_t len) {
 // the hex-prefix path over nibbles [n0, n1) of key, as an RLP item (pack_nibbles)
 PV_HD uint64_t tb_hp_len(uint64_t n0, uint64_t n1) {
   const uint64_t hb = (n1 - n0) / 2 + 1;
-  return hb == 1 ? 1 : rlp_list_header_len(hb) + hb;   // one byte is a flag byte below 0x40: itself
+  return hb == 1 ? 1 : rlp_header_len(hb) + hb;   // one byte is a flag byte below 0x40: itself
 }
 
 PV_HD uint8_t* tb_put_hp(uint8_t* w, const uint8_t* key, uint64_t n0, uint64_t n1, bool leaf) {
@@ -424,7 +417,7 @@ PV_HD void tb_size_one(const TbCtx& c, uint32_t e) {
     return;
   }
   const uint64_t body = tb_payload(c, e);
-  const uint64_t len = rlp_list_header_len(body) + body;
+  const uint64_t len = rlp_header_len(body) + body;
   const bool emit = len >= 32 || e == *c.root_e;
   c.elen[e] = (uint32_t)len;
   c.off[e] = emit ? len : 0;
@@ -441,7 +434,7 @@ PV_HD void tb_emit_one(const TbCtx& c, uint32_t e) {
   uint8_t* const dst = emit ? c.out_blob + c.off[e] : c.inl + 32 * (uint64_t)e;
   uint32_t hl = 1;   // the list header's length: the one hl with header_len(len - hl) == hl
   for (uint32_t t = 1; t <= 9 && t < len; ++t)
-    if (rlp_list_header_len(len - t) == t) {
+    if (rlp_header_len(len - t) == t) {
       hl = t;
       break;
     }

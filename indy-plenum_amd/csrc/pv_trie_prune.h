@@ -6,26 +6,23 @@
 // to readers; state/pruning_state.py:87-102) and the store keeps exactly the
 // nodes some sg_walk from one of those roots can fetch by hash.
 //
-// Mark rule, for one stored node (an RLP list whose payload fills it exactly):
-//   17 items  items 0 .. 15 are children; item 16 is a value, never a reference
-//   2 items   item 0 is a non-empty string whose high nibble gives the kind: a
-//             leaf (flag 2) has no child, an extension's item 1 is its child
-//             (an extension with an empty path ends every walk SP_MALFORMED and
-//             has no child either)
-//   child     a list: an inline node, visited in place by the same rule, never
-//             looked up and never counted; a string of exactly 32 bytes: a
-//             reference, resolved with ts_find -- found: the slot holder (the
-//             lowest id among duplicates) is marked, not found: counted as
-//             missing (a store filled from proofs is partial by design, and a
-//             walk that needs that node answered SP_NODE_MISSING before and
-//             still does); any other string: no reference
-// A node, or an inline node, that does not parse at its own level -- not a list
-// that fills its range, an item that overruns it, an 18th item, another item
-// count, item 0 a list or empty -- contributes no children: every walk through
-// it ended SP_MALFORMED without fetching further.  The stored node that holds
-// it is still kept.  A 32-byte leaf value or branch value is never followed.
-// Bounds discipline as sg_walk: no byte is read before its length is checked
-// against the enclosing node.
+// Mark rule, for one stored node (the grammar is in pv_trie_node.h):
+//   branch      items 0 .. 15 are children; item 16 is a value, never a reference
+//   leaf        no child
+//   extension   item 1 is its child (an extension over no nibble ends every walk
+//               SP_MALFORMED and has no child either)
+//   child       a list: an inline node, visited in place by the same rule, never
+//               looked up and never counted; a string of exactly 32 bytes: a
+//               reference, resolved with ts_find -- found: the slot holder (the
+//               lowest id among duplicates) is marked, not found: counted as
+//               missing (a store filled from proofs is partial by design, and a
+//               walk that needs that node answered SP_NODE_MISSING before and
+//               still does); any other string: no reference
+// A node, or an inline node, that does not parse at its own level (tn_scan or
+// tn_path refuses it, or it has another item count than 2 or 17) contributes no
+// children: every walk through it ended SP_MALFORMED without fetching further.
+// The stored node that holds it is still kept.  A 32-byte leaf value or branch
+// value is never followed.
 //
 // Inline nesting.  A well-formed trie nests inline nodes at most 3 deep under a
 // hashed node (extension -> branch -> leaf: an inline node is under 32 bytes and
@@ -112,21 +109,17 @@ PV_HD uint32_t tp_resolve(const TpCtx& c, const uint32_t t[8]) {
 template <int LEVELS>
 PV_HD void tp_visit(const TpCtx& c, uint64_t cb, uint64_t ce);
 
-// one child item: [pos, ie) with payload [ib, ie)
+// one child item
 template <int LEVELS>
-PV_HD void tp_child(const TpCtx& c, uint64_t pos, bool il, uint64_t ib, uint64_t ie) {
-  if (il) {
+PV_HD void tp_child(const TpCtx& c, const TnItem& it) {
+  if (it.l) {
     if constexpr (LEVELS == 0) tp_count(c.counts + TP_OVERFLOW);
-    else tp_visit<LEVELS - 1>(c, pos, ie);
+    else tp_visit<LEVELS - 1>(c, it.s, it.e);
     return;
   }
-  if (ie - ib != 32) return;
+  if (it.e - it.b != 32) return;
   uint32_t t[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const uint8_t* q = c.blob + ib + 4 * k;
-    t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-  }
+  tn_load_ref(c.blob + it.b, t);
   if (tp_resolve(c, t) == TS_ABSENT) tp_count(c.counts + TP_MISSING);
 }
 
@@ -136,47 +129,23 @@ PV_HD void tp_child(const TpCtx& c, uint64_t pos, bool il, uint64_t ib, uint64_t
 template <int LEVELS>
 PV_HD void tp_visit(const TpCtx& c, uint64_t cb, uint64_t ce) {
   const uint8_t* blob = c.blob;
-  bool is_list;
-  uint64_t pb, pe;
-  if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) return;
-  uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0;
-  bool i0l = false, i1l = false;
-  uint32_t count = 0;
-  uint64_t pos = pb;
-  while (pos < pe) {
-    bool il;
-    uint64_t ib, ie;
-    if (count == 17 || !rlp_item(blob, pos, pe, il, ib, ie)) return;
-    if (count == 0) {
-      i0b = ib;
-      i0e = ie;
-      i0l = il;
-    }
-    if (count == 1) {
-      i1s = pos;
-      i1b = ib;
-      i1e = ie;
-      i1l = il;
-    }
-    pos = ie;
-    ++count;
-  }
-  if (count == 2) {
-    if (i0l || i0e == i0b) return;
-    const uint32_t flags = blob[i0b] >> 4;
-    if (flags & 2u) return;                                        // a leaf: item 1 is its value
-    if (2 * (i0e - i0b - 1) + (flags & 1u) == 0) return;           // an extension over no nibble
-    tp_child<LEVELS>(c, i1s, i1l, i1b, i1e);
+  TnScan n;
+  if (!tn_scan(blob, cb, ce, TN_NO_SLOT, n)) return;
+  if (n.count == 2) {
+    TnPath h;
+    if (!tn_path(blob, n.i0, h)) return;
+    if (h.leaf) return;      // item 1 is its value
+    if (h.pn == 0) return;   // an extension over no nibble
+    tp_child<LEVELS>(c, n.i1);
     return;
   }
-  if (count != 17) return;
-  pos = pb;
+  if (n.count != 17) return;
+  TnItem it;
+  it.e = n.pb;
   for (uint32_t k = 0; k < 16; ++k) {
-    bool il;
-    uint64_t ib, ie;
-    if (!rlp_item(blob, pos, pe, il, ib, ie)) return;   // parsed by the first scan: never
-    tp_child<LEVELS>(c, pos, il, ib, ie);
-    pos = ie;
+    it.s = it.e;
+    if (!rlp_item(blob, it.s, n.pe, it.l, it.b, it.e)) return;   // parsed by the first scan: never
+    tp_child<LEVELS>(c, it);
   }
 }
 

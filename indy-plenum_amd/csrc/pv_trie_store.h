@@ -33,13 +33,12 @@
 // sequential host twin (ids ascending) gives.  Only 1 is ever written to dup[]
 // (it is zeroed before the launch), each flagged id by exactly one lane.
 //
-// The walk (sg_walk) makes the decisions of sp_verify (pv_trie_proof.h) with
-// the same bounds discipline -- no byte is read before its length is checked
-// against the enclosing node, at most 2 len(key) + 1 steps -- but resolves
-// 32-byte child references with ts_find and records, instead of a verdict, the
-// id of every node fetched by hash in walk order (root first), the byte range
-// of the terminal value and a status.  Inline nodes are walked in place and are
-// not proof nodes, as in the reference (spv_grabbing runs only on db fetches).
+// The walk (sg_walk) descends by the step sp_verify takes (tn_step,
+// pv_trie_node.h), at most 2 len(key) + 1 times, but resolves 32-byte child
+// references with ts_find and records, instead of a verdict, the id of every
+// node fetched by hash in walk order (root first), the byte range of the
+// terminal value and a status.  Inline nodes are walked in place and are not
+// proof nodes, as in the reference (spv_grabbing runs only on db fetches).
 //
 // The serialized proof is rlp(list of nodes) (Trie.serialize_proof,
 // :1164-1170) with the nodes in REVERSE walk order: terminal node first, root
@@ -128,21 +127,6 @@ PV_HD bool ts_insert(uint32_t* table, uint32_t slots, const uint32_t* dig, uint8
   return false;
 }
 
-// length (1 .. 9) of the RLP list header over a payload of `body` bytes ...
-PV_HD uint32_t rlp_list_header_len(uint64_t body) {
-  if (body < 56) return 1;
-  uint32_t ll = 0;
-  for (uint64_t v = body; v; v >>= 8) ++ll;
-  return 1 + ll;
-}
-
-// ... and its byte k < hl (hl = that length): no array, so that one lane per byte can write it
-PV_HD uint8_t rlp_list_header_byte(uint64_t body, uint32_t hl, uint32_t k) {
-  if (hl == 1) return (uint8_t)(192 + body);
-  if (k == 0) return (uint8_t)(247 + (hl - 1));
-  return (uint8_t)(body >> (8 * (hl - 1 - k)));
-}
-
 struct SgResult {
   uint32_t status;       // SP_OK, SP_NODE_MISSING, SP_MALFORMED or SP_PATH_TOO_LONG
   uint32_t node_count;   // hashed nodes fetched (the true count, also above max_nodes)
@@ -176,106 +160,21 @@ PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end
   uint64_t nib = 0;   // key nibbles consumed
   uint32_t st = SP_MALFORMED;   // the step bound ran out
   for (uint64_t step = 0; step <= total; ++step) {
-    bool is_list;
-    uint64_t pb, pe;
-    if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) break;
-    const uint32_t sel = nib < total ? sp_nibble(key, nib) : 16u;
-    uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0, sls = 0, slb = 0, sle = 0;
-    bool i0l = false, i1l = false, sll = false, bad = false;
-    uint32_t count = 0;
-    uint64_t pos = pb;
-    while (pos < pe) {
-      bool il;
-      uint64_t ib, ie;
-      if (count == 17 || !rlp_item(blob, pos, pe, il, ib, ie)) {
-        bad = true;
-        break;
-      }
-      if (count == 0) {
-        i0b = ib;
-        i0e = ie;
-        i0l = il;
-      }
-      if (count == 1) {
-        i1s = pos;
-        i1b = ib;
-        i1e = ie;
-        i1l = il;
-      }
-      if (count == sel) {
-        sls = pos;
-        slb = ib;
-        sle = ie;
-        sll = il;
-      }
-      pos = ie;
-      ++count;
-    }
-    if (bad) break;
-    uint64_t rs, rb, re;   // the child reference (or, with `done`, the value): start, payload
-    bool rl, done = false;
-    if (count == 17) {
-      rs = sls;
-      rb = slb;
-      re = sle;
-      rl = sll;
-      if (nib == total) done = true;
-      else ++nib;
-    } else if (count == 2) {
-      if (i0l || i0e == i0b) break;
-      const uint8_t* p = blob + i0b;
-      const uint32_t flags = p[0] >> 4;
-      const uint32_t odd = flags & 1u;
-      const uint64_t pn = 2 * (i0e - i0b - 1) + odd;   // path nibbles
-      const uint64_t skip = 2 - odd;
-      const uint64_t left = total - nib;
-      const bool leaf = (flags & 2u) != 0;
-      if (!leaf && pn == 0) break;
-      bool match = leaf ? pn == left : pn <= left;
-      if (match) {
-        uint32_t diff = 0;
-        for (uint64_t i = 0; i < pn; ++i) diff |= sp_nibble(p, skip + i) ^ sp_nibble(key, nib + i);
-        match = diff == 0;
-      }
-      if (!match) {   // blank: proven absent
-        st = SP_OK;
-        break;
-      }
-      rs = i1s;
-      rb = i1b;
-      re = i1e;
-      rl = i1l;
-      if (leaf) done = true;
-      else nib += pn;
-    } else {
-      break;
-    }
-    if (done) {
-      if (rl) break;
-      r.val_beg = rb;
-      r.val_len = re - rb;
-      st = SP_OK;
-      break;
-    }
-    if (rl) {   // an inline node: its RLP is the item itself, and it is no proof node
-      cb = rs;
-      ce = re;
+    uint64_t ob, oe;
+    uint32_t t[8];
+    const uint32_t next = tn_step(blob, cb, ce, key, total, nib, ob, oe, t);
+    if (next == TN_INLINE) {   // walked in place, and no proof node
+      cb = ob;
+      ce = oe;
       continue;
     }
-    const uint64_t rlen = re - rb;
-    if (rlen == 0) {   // blank: proven absent
-      st = SP_OK;
+    if (next != TN_HASHED) {   // the walk ends here; TN_ABSENT: proven absent
+      if (next == TN_VALUE) {
+        r.val_beg = ob;
+        r.val_len = oe - ob;
+      }
+      st = next == TN_MALFORMED ? SP_MALFORMED : next == TN_MISSING ? SP_NODE_MISSING : SP_OK;
       break;
-    }
-    if (rlen != 32) {
-      st = SP_NODE_MISSING;
-      break;
-    }
-    uint32_t t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint8_t* q = blob + rb + 4 * k;
-      t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
     }
     j = ts_find(table, slots, dig, n_nodes, t);
     if (j == TS_ABSENT) {
@@ -299,7 +198,7 @@ PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end
 PV_HD void sg_outputs(const SgResult& r, uint64_t& proof_len, uint64_t& val_rel, uint64_t& val_len) {
   proof_len = val_rel = val_len = 0;
   if (r.status != SP_OK) return;
-  const uint32_t h = rlp_list_header_len(r.body_len);
+  const uint32_t h = rlp_header_len(r.body_len);
   proof_len = h + r.body_len;
   if (r.val_len) {
     val_rel = h + (r.val_beg - r.last_beg);
@@ -321,7 +220,7 @@ PV_HD bool sg_pack_check(const uint64_t* beg, const uint64_t* end, uint32_t n_no
     if (id >= n_nodes) return false;
     body += end[id] - beg[id];
   }
-  return rlp_list_header_len(body) + body == len;
+  return rlp_header_len(body) + body == len;
 }
 
 }  // namespace pv

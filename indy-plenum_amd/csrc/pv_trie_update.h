@@ -40,9 +40,9 @@
 // group ends up first without a stack.
 //
 // Bounds.  Every loop is bounded by a key length, a path length checked against
-// its node, 17 items or 33 reference bytes; no length is read before it is
-// checked against the enclosing node; no lane keeps an array it indexes at run
-// time.  A missing or malformed node gives the key a PV_SP_* status and the
+// its node, 17 items or 33 reference bytes; the nodes are read through the
+// parser of pv_trie_node.h (tn_scan, tn_path); no lane keeps an array it
+// indexes at run time.  A missing or malformed node gives the key a PV_SP_* status and the
 // caller refuses the whole call.
 //
 // Removals (tu_walk_t<true>, behind pv_state_apply).  A batch item with an empty
@@ -105,18 +105,20 @@ struct TuCur {
   uint64_t i, k, v;   // item index, path byte offset, payload byte offset (count mode: sizes)
 };
 
-// A child reference item [start, ie) with payload [ib, ie): SP_OK and ref_len =
-// 0 (blank) or the bytes to carry from `start`; hashed = a 32-byte hash.
-PV_HD uint32_t tu_ref(uint64_t start, bool il, uint64_t ib, uint64_t ie, uint64_t& ref_len, bool& hashed) {
+// A child reference item: SP_OK and ref_len = 0 (blank) or the bytes to carry
+// from its start; hashed = a 32-byte hash.  Stricter than the reading walks: an
+// inline node is under 32 bytes and a hash has the one-byte header 0xa0, since
+// the bytes are carried into the new trie as they are.
+PV_HD uint32_t tu_ref(const TnItem& it, uint64_t& ref_len, bool& hashed) {
   ref_len = 0;
   hashed = false;
-  if (il) {
-    if (ie - start >= 32) return SP_MALFORMED;
-    ref_len = ie - start;
+  if (it.l) {
+    if (it.e - it.s >= 32) return SP_MALFORMED;
+    ref_len = it.e - it.s;
     return SP_OK;
   }
-  if (ie == ib) return SP_OK;
-  if (ie - ib != 32 || ib != start + 1) return SP_NODE_MISSING;
+  if (it.e == it.b) return SP_OK;
+  if (it.e - it.b != 32 || it.b != it.s + 1) return SP_NODE_MISSING;
   ref_len = 33;
   hashed = true;
   return SP_OK;
@@ -191,49 +193,29 @@ PV_HD uint32_t tu_open(const TuCtx& c, uint64_t pos, uint64_t rlen, bool hashed,
   uint64_t cb = pos, ce = pos + rlen;
   if (hashed) {
     uint32_t t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint8_t* q = blob + pos + 1 + 4 * k;
-      t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
+    tn_load_ref(blob + pos + 1, t);
     const uint32_t id = ts_find(c.table, c.slots, c.dig, c.n_nodes, t);
     if (id == TS_ABSENT) return SP_NODE_MISSING;
     cb = c.beg[id];
     ce = c.end[id];
   }
-  bool is_list;
-  uint64_t pb, pe;
-  if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) return SP_MALFORMED;
-  uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0;
-  bool i0l = false, i1l = false;
-  uint32_t count = 0;
-  uint64_t at = pb;
-  while (at < pe) {
-    bool il;
-    uint64_t ib, ie;
-    if (count == 17 || !rlp_item(blob, at, pe, il, ib, ie)) return SP_MALFORMED;
-    if (count == 0) i0b = ib, i0e = ie, i0l = il;
-    if (count == 1) i1s = at, i1b = ib, i1e = ie, i1l = il;
-    at = ie;
-    ++count;
-  }
-  if (count == 17) return SP_OK;
-  if (count != 2 || i0l || i0e == i0b) return SP_MALFORMED;
-  const uint8_t* p = blob + i0b;
-  const uint32_t flags = p[0] >> 4, odd = flags & 1u;
-  const uint64_t pn = 2 * (i0e - i0b - 1) + odd, skip = 2 - odd;
-  if (flags & 2u) {
-    if (i1l || i1e == i1b) return SP_MALFORMED;
-    o = TuOpen{TU_VALUE, p, skip, pn, blob + i1b, i1e - i1b};
+  TnScan n;
+  if (!tn_scan(blob, cb, ce, TN_NO_SLOT, n)) return SP_MALFORMED;
+  if (n.count == 17) return SP_OK;
+  TnPath h;
+  if (n.count != 2 || !tn_path(blob, n.i0, h)) return SP_MALFORMED;
+  if (h.leaf) {
+    if (n.i1.l || n.i1.e == n.i1.b) return SP_MALFORMED;
+    o = TuOpen{TU_VALUE, h.p, h.skip, h.pn, blob + n.i1.b, n.i1.e - n.i1.b};
     return SP_OK;
   }
-  if (pn == 0) return SP_MALFORMED;
+  if (h.pn == 0) return SP_MALFORMED;
   uint64_t len;
   bool h2;
-  const uint32_t r = tu_ref(i1s, i1l, i1b, i1e, len, h2);
+  const uint32_t r = tu_ref(n.i1, len, h2);
   if (r != SP_OK) return r;
   if (len == 0) return SP_MALFORMED;
-  o = TuOpen{TU_SUBTREE, p, skip, pn, blob + i1s, len};
+  o = TuOpen{TU_SUBTREE, h.p, h.skip, h.pn, blob + n.i1.s, len};
   return SP_OK;
 }
 
@@ -279,39 +261,20 @@ PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
   uint64_t cb = c.beg[id], ce = c.end[id], D = 0;
   uint32_t st = SP_MALFORMED;   // the step bound ran out
   for (uint64_t step = 0; step <= knib; ++step) {
-    bool is_list;
-    uint64_t pb, pe;
-    if (!rlp_item(blob, cb, ce, is_list, pb, pe) || !is_list || pe != ce) break;
     const bool first = hl <= D, last = hr <= D;
     const int32_t s = D < knib ? (int32_t)sp_nibble(key, D) : -1;
     const int32_t s_prev = (!first && D < pnib) ? (int32_t)sp_nibble(kp, D) : -1;
-    // first scan: the shape, item 0 and 1, slot s, item 16, the AFTER group's size
-    uint64_t i0b = 0, i0e = 0, i1s = 0, i1b = 0, i1e = 0, sls = 0, slb = 0, sle = 0, vb = 0, ve = 0;
-    bool i0l = false, i1l = false, sll = false, vl = false;
-    uint32_t count = 0, bad = SP_OK;
-    TuCur grp{0, 0, 0};
-    uint64_t pos = pb;
-    while (pos < pe) {
-      bool il;
-      uint64_t ib, ie;
-      if (count == 17 || !rlp_item(blob, pos, pe, il, ib, ie)) {
-        bad = SP_MALFORMED;
-        break;
-      }
-      if (count == 0) i0b = ib, i0e = ie, i0l = il;
-      if (count == 1) i1s = pos, i1b = ib, i1e = ie, i1l = il;
-      if ((int32_t)count == s) sls = pos, slb = ib, sle = ie, sll = il;
-      if (count == 16) vb = ib, ve = ie, vl = il;
-      pos = ie;
-      ++count;
-    }
-    if (bad != SP_OK || (count != 17 && count != 2)) break;
-    uint64_t rs, rb, re;   // the child the walk goes on in
-    bool rl;
-    if (count == 17) {
-      if (vl) break;
+    // first scan: the shape, item 0 and 1, slot s, item 16
+    TnScan n;
+    if (!tn_scan(blob, cb, ce, (uint32_t)s, n) || (n.count != 17 && n.count != 2)) break;
+    uint32_t bad = SP_OK;
+    TuCur grp{0, 0, 0};   // the AFTER group's size
+    TnItem r;             // the child the walk goes on in
+    if (n.count == 17) {
+      if (n.i16.l) break;
       // second scan: the carried slots, checked; in write mode also written
-      if (ve > vb && first && knib != D) tu_put(c, write, front, key, D, key, 0, 0, 16, TU_VALUE, blob + vb, ve - vb);
+      if (n.i16.e > n.i16.b && first && knib != D)
+        tu_put(c, write, front, key, D, key, 0, 0, 16, TU_VALUE, blob + n.i16.b, n.i16.e - n.i16.b);
       for (uint32_t pass = 0; pass < 2 && bad == SP_OK; ++pass) {
         // pass 0 sizes the AFTER group (and counts BEFORE in count mode); pass 1 writes
         if (pass == 1 && !write) break;
@@ -320,20 +283,21 @@ PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
           back.i -= grp.i, back.k -= grp.k, back.v -= grp.v;
           w = back;
         }
-        pos = pb;
+        uint64_t pos = n.pb;
         for (int32_t t = 0; t < 16; ++t) {
-          bool il;
-          uint64_t ib, ie, rlen;
+          TnItem it;
+          it.s = pos;
+          uint64_t rlen;
           bool hashed;
-          if (!rlp_item(blob, pos, pe, il, ib, ie)) {   // parsed by the first scan: never
+          if (!rlp_item(blob, pos, n.pe, it.l, it.b, it.e)) {   // parsed by the first scan: never
             bad = SP_MALFORMED;
             break;
           }
           const bool before = t > s_prev && t < s, after = last && t > s;
           if (before || after) {
-            const uint32_t r = tu_ref(pos, il, ib, ie, rlen, hashed);
-            if (r != SP_OK) {
-              bad = r;
+            const uint32_t rr = tu_ref(it, rlen, hashed);
+            if (rr != SP_OK) {
+              bad = rr;
               break;
             }
             if (rlen) {
@@ -350,7 +314,7 @@ PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
               }
             }
           }
-          pos = ie;
+          pos = it.e;
         }
       }
       if (bad != SP_OK) {
@@ -362,53 +326,51 @@ PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
         st = SP_OK;
         break;
       }
-      rs = sls, rb = slb, re = sle, rl = sll;
+      r = n.sel;
       D += 1;
     } else {
-      if (i0l || i0e == i0b) break;
-      const uint8_t* p = blob + i0b;
-      const uint32_t flags = p[0] >> 4, odd = flags & 1u;
-      const uint64_t pn = 2 * (i0e - i0b - 1) + odd, skip = 2 - odd;
-      const bool leaf = (flags & 2u) != 0;
-      if (!leaf && pn == 0) break;
-      if (leaf && (i1l || i1e == i1b)) break;
-      const uint32_t cq = tu_cmp(p, skip, pn, key, D, knib);
+      TnPath h;
+      if (!tn_path(blob, n.i0, h)) break;
+      const bool leaf = h.leaf;
+      if (!leaf && h.pn == 0) break;
+      if (leaf && (n.i1.l || n.i1.e == n.i1.b)) break;
+      const uint32_t cq = tu_cmp(h.p, h.skip, h.pn, key, D, knib);
       if (leaf && cq == 0) {   // overwritten
         st = SP_OK;
         break;
       }
       if (!leaf && cq <= 1) {   // dissolved
-        rs = i1s, rb = i1b, re = i1e, rl = i1l;
-        D += pn;
+        r = n.i1;
+        D += h.pn;
       } else {
-        const uint8_t* src = blob + i1b;
-        uint64_t len = i1e - i1b;
+        const uint8_t* src = blob + n.i1.b;
+        uint64_t len = n.i1.e - n.i1.b;
         if (!leaf) {
           bool hashed;
-          const uint32_t r = tu_ref(i1s, i1l, i1b, i1e, len, hashed);
-          if (r != SP_OK || len == 0) {
-            st = r != SP_OK ? r : (uint32_t)SP_MALFORMED;
+          const uint32_t rr = tu_ref(n.i1, len, hashed);
+          if (rr != SP_OK || len == 0) {
+            st = rr != SP_OK ? rr : (uint32_t)SP_MALFORMED;
             break;
           }
-          src = blob + i1s;
+          src = blob + n.i1.s;
         }
         const uint8_t kind = leaf ? TU_VALUE : TU_SUBTREE;
         if (cq == 1 || cq == 3) {
           bool mine = first;
           if (!mine) {
-            const uint32_t cp = tu_cmp(p, skip, pn, kp, D, pnib);
+            const uint32_t cp = tu_cmp(h.p, h.skip, h.pn, kp, D, pnib);
             mine = cp == 2 || cp == 4;
           }
-          if (mine) tu_put(c, write, front, key, D, p, skip, pn, 16, kind, src, len);
+          if (mine) tu_put(c, write, front, key, D, h.p, h.skip, h.pn, 16, kind, src, len);
         } else if (last) {
           if (write) {
             TuCur one{0, 0, 0};
-            tu_put(c, false, one, key, D, p, skip, pn, 16, kind, src, len);
+            tu_put(c, false, one, key, D, h.p, h.skip, h.pn, 16, kind, src, len);
             back.i -= one.i, back.k -= one.k, back.v -= one.v;
             TuCur w = back;
-            tu_put(c, true, w, key, D, p, skip, pn, 16, kind, src, len);
+            tu_put(c, true, w, key, D, h.p, h.skip, h.pn, 16, kind, src, len);
           } else {
-            tu_put(c, false, front, key, D, p, skip, pn, 16, kind, src, len);
+            tu_put(c, false, front, key, D, h.p, h.skip, h.pn, 16, kind, src, len);
           }
         }
         st = SP_OK;
@@ -417,26 +379,22 @@ PV_HD uint32_t tu_walk_t(const TuCtx& c, uint64_t j, bool write) {
     }
     uint64_t rlen;
     bool hashed;
-    const uint32_t r = tu_ref(rs, rl, rb, re, rlen, hashed);
-    if (r != SP_OK) {
-      st = r;
+    const uint32_t rr = tu_ref(r, rlen, hashed);
+    if (rr != SP_OK) {
+      st = rr;
       break;
     }
     if (rlen == 0) {   // a blank slot ends the walk; an extension over nothing is no node
-      st = count == 17 ? (uint32_t)SP_OK : (uint32_t)SP_MALFORMED;
+      st = n.count == 17 ? (uint32_t)SP_OK : (uint32_t)SP_MALFORMED;
       break;
     }
     if (!hashed) {
-      cb = rs;
-      ce = re;
+      cb = r.s;
+      ce = r.e;
       continue;
     }
     uint32_t t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint8_t* q = blob + rb + 4 * k;
-      t[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
+    tn_load_ref(blob + r.b, t);
     id = ts_find(c.table, c.slots, c.dig, c.n_nodes, t);
     if (id == TS_ABSENT) {
       st = SP_NODE_MISSING;

@@ -11,6 +11,7 @@ import pytest
 import _state_apply as sa
 import _state_build as sb
 import _state_update as su
+import _trie_hostile as th
 from plenum_gpu.state_proofs import BLANK_ROOT, PV_SP_MALFORMED, PV_SP_NODE_MISSING, rlp_encode
 from plenum_gpu.state_store import (ITEM_SUBTREE, ITEM_VALUE, apply_encoded_host, apply_host, build_encoded_host,
                                     build_host, merge_host, update_encoded_host, update_host, walk_host)
@@ -308,6 +309,9 @@ def test_asan_program(tmp_path):
         st.add_nodes([junk, leaf, root_node])
         cases.append(([junk, leaf, root_node], sb.sha3(root_node), [(b'\x20', b'')],
                       st.apply(sb.sha3(root_node), [(b'\x20', b'')], insert=False)))
+    for row in th.ROWS:                                 # the hostile-node table
+        cases += [(row.nodes, row.root, batch, th.apply_twin(row, batch))
+                  for batch in th.UPDATE_BATCHES + th.REMOVAL_BATCHES]
     assert {c[3].rc for c in cases} >= {sa.OK, sa.BAD_ORDER, sa.BAD_WALK}
     assert {c[3].status for c in cases} >= {0, PV_SP_NODE_MISSING, PV_SP_MALFORMED}
     path = os.path.join(str(tmp_path), 'cases.bin')

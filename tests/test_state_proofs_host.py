@@ -10,12 +10,14 @@ answers False for all of them by rule (Row.expected)."""
 import hashlib
 import os
 import random
+import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 import _state_proofs as sp
+import _trie_hostile as th
 
 BOUNDARY = [0, 1, 135, 136, 137, 271, 272, 273, 407, 408, 1000]
 
@@ -235,11 +237,24 @@ def test_multi_without_pairs_is_true_iff_the_root_node_is_there(rows, mirror):
                                              (r.root, dict(r.kvs), r.serialized)]).tolist() == [True, False, True]
 
 
-def test_header_self_check_under_sanitizers():
+def test_header_self_check_under_sanitizers(tmp_path):
     """tools/hostcheck/stateproofcheck_main.cpp: its own process, built with
-    AddressSanitizer + UBSan; SHA3 at every offset of exact-size buffers and the
-    walk over truncated, flipped and random node bytes"""
+    AddressSanitizer + UBSan; SHA3 at every offset of exact-size buffers, the
+    walk over truncated, flipped and random node bytes, and the hostile-node
+    table as a case file"""
     subprocess.run(['make', '-s', '-C', sp.HC_DIR, 'stateproofcheck_asan'], check=True)
-    r = subprocess.run([os.path.join(sp.HC_DIR, 'stateproofcheck_asan')], capture_output=True, text=True, timeout=120)
+    cases = []
+    for row in th.ROWS:
+        proved = [th.prove_twin(row)[0].value(q) for q in range(len(th.PROVE_KEYS))]
+        cases += [(row, key, val, th.verify_twin(row, key, val)) for _, key, val in th.verify_queries(row, proved)]
+    lenb = lambda b: struct.pack('<Q', len(b)) + b  # noqa: E731
+    path = str(tmp_path / 'cases.bin')
+    with open(path, 'wb') as fh:
+        fh.write(b'SVC1' + struct.pack('<I', len(cases)))
+        for row, key, val, status in cases:
+            fh.write(struct.pack('<Q', len(row.nodes)) + b''.join(lenb(n) for n in row.nodes) + row.root +
+                     lenb(key) + lenb(val) + struct.pack('<I', status))
+    r = subprocess.run([os.path.join(sp.HC_DIR, 'stateproofcheck_asan'), path], capture_output=True, text=True,
+                       timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert 'stateproofcheck ok' in r.stdout
+    assert 'stateproofcheck: {} cases ok'.format(len(cases)) in r.stdout and 'stateproofcheck ok' in r.stdout

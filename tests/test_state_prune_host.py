@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import _state_prune as pr
+import _trie_hostile as th
 from plenum_gpu.state_proofs import BLANK_ROOT, PV_SP_MALFORMED, PV_SP_NODE_MISSING, PV_SP_OK
 from plenum_gpu.state_store import apply_host, build_host, reachable_host, update_host, walk_host
 
@@ -181,6 +182,7 @@ def test_asan_program(tmp_path):
     full = {pr.sha3(n): n for n in pr.filled('rm/mixed300')[0]}
     proof = walk_host(full, roots[-1], next(iter(full.values()))[:3])[1]
     cases.append((proof, roots[-1:], pr.Want(proof, roots[-1:])))
+    cases += [(row.nodes, [row.root], th.prune_want(row)) for row in th.ROWS]      # the hostile-node table
     assert any(w is not None and w.n_missing for _, _, w in cases)
     assert any(w is not None and PV_SP_NODE_MISSING in w.root_status for _, _, w in cases)
     path = os.path.join(str(tmp_path), 'cases.bin')

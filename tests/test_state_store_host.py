@@ -15,6 +15,7 @@ import pytest
 
 import _state_proofs as sp
 import _state_store as ss
+import _trie_hostile as th
 
 
 def run_host(sc):
@@ -214,7 +215,7 @@ def test_every_scenario_under_sanitizers(tmp_path):
     AddressSanitizer + UBSan; insert, walk and pack of every scenario above with every
     buffer at its exact size, outputs equal to the host build's"""
     cases = []
-    for sc in [f() for f in ss.SCENARIOS.values()] + ss.sc_missing():
+    for sc in [f() for f in ss.SCENARIOS.values()] + ss.sc_missing() + [th.prove_scenario(r) for r in th.ROWS]:
         got, _, st = run_host(sc)
         info = st.info()
         batches, roots, ridx, keys, max_nodes = sc

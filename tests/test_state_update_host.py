@@ -10,6 +10,7 @@ import pytest
 
 import _state_build as sb
 import _state_update as su
+import _trie_hostile as th
 from plenum_gpu.state_proofs import BLANK_ROOT, PV_SP_MALFORMED, PV_SP_NODE_MISSING
 from plenum_gpu.state_store import (ITEM_SUBTREE, ITEM_VALUE, build_encoded_host, build_host, merge_host,
                                     update_encoded_host, update_host, walk_host)
@@ -242,6 +243,8 @@ def test_asan_program(tmp_path):
         for root, bad in ((b0.root, swapped), (b0.root, batch), (sb.sha3(b'?'), batch), (b0.root, []),
                           (BLANK_ROOT, batch), (b0.root, batch[:2] + [(batch[2][0], b'')])):
             cases.append((b0.nodes()[1:], root, bad, st.update(root, bad, insert=False)))
+    for row in th.ROWS:                                 # the hostile-node table
+        cases += [(row.nodes, row.root, batch, th.update_twin(row, batch)) for batch in th.UPDATE_BATCHES]
     assert {c[3].rc for c in cases} >= {su.OK, su.BAD_ORDER, su.BAD_VALUE, su.BAD_WALK}
     path = os.path.join(str(tmp_path), 'cases.bin')
     su.write_cases(path, cases)

@@ -20,7 +20,7 @@ assembly, by instruction class, against that mix at the measured per-instruction
 rates (the newest profiles/*int_rates.json scaled to the best v_mad_u64_u32
 ceiling of profiles/r01_mad_peak.json).  CPU comparands, one thread on this
 host: hashlib.sha3_256 and the Python mirror's walk (a port, not the reference).
-Writes one JSON line to profiles/state_proofs.json.  Without a GPU it fails.
+Writes one JSON line to profiles/state_proofs.json (--out names another file).  Without a GPU it fails.
 """
 import argparse
 import ctypes
@@ -312,7 +312,7 @@ def run(a):
     res['cpu_python_mirror_queries_per_s'] = k / (time.perf_counter() - t0)
     assert (mst == st[:k]).all(), 'the mirror and the GPU disagree'
     os.makedirs(os.path.join(REPO, 'profiles'), exist_ok=True)
-    with open(os.path.join(REPO, 'profiles', 'state_proofs.json'), 'w') as fh:
+    with open(a.out, 'w') as fh:
         fh.write(json.dumps(res) + '\n')
     for name, s in res['shapes'].items():
         print(name, {k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items() if k != 'runs'})
@@ -325,6 +325,7 @@ def main():
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--window', type=float, default=0.5)
     ap.add_argument('--proofs', type=int, default=1 << 18)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'state_proofs.json'))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_state_proofs: no GPU (a measurement needs one)')

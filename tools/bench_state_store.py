@@ -19,7 +19,7 @@ random present keys, as in profiles/state_proofs.json.  Shapes:
 
 and, one thread on this host, the Python mirror walk_host (a port, not the
 reference) on the first 2,000 queries.  Writes one JSON line to
-profiles/state_store.json.  Without a GPU it fails.
+profiles/state_store.json (--out names another file).  Without a GPU it fails.
 """
 import argparse
 import ctypes
@@ -202,7 +202,7 @@ def run(a):
     for i in range(0, k, 97):
         assert mirror[i][3] == h_out[int(h_off[i]):int(h_off[i + 1])].tobytes(), 'the mirror and the GPU disagree'
     os.makedirs(os.path.join(REPO, 'profiles'), exist_ok=True)
-    with open(os.path.join(REPO, 'profiles', 'state_store.json'), 'w') as fh:
+    with open(a.out, 'w') as fh:
         fh.write(json.dumps(res) + '\n')
     for name, s in res['shapes'].items():
         print(name, {k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items() if k != 'runs'})
@@ -215,6 +215,7 @@ def main():
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--window', type=float, default=0.5)
     ap.add_argument('--queries', type=int, default=1 << 18)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'state_store.json'))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_state_store: no GPU (a measurement needs one)')

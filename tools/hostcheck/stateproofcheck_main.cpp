@@ -10,6 +10,8 @@
 //   digest, so the walk does enter it -- run on a heap copy that ends exactly
 //   at the node's last byte.  Every status must be one of SP_*, and the
 //   sanitizers must stay silent.
+//   With a case file as its argument: each case's walk, over the same exact-size
+//   copies, must give the recorded status.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -92,7 +94,7 @@ void root_of(uint8_t root[32], const std::vector<uint8_t>& node) { sha3_at(root,
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
   // ---- SHA3-256
   uint8_t want[32], got[32];
   from_hex(want, "a7ffc6f8bf1ed76651c14756a061d662f580ff4de43b49fa82d80a4b80f8434a", 32);
@@ -186,6 +188,34 @@ int main() {
     if (ok)
       for (uint64_t k = 0; k < count; ++k) CHECK(ib[k] < ie[k] && ie[k] <= t.size());
     free(exact);
+  }
+  // ---- a case file (tests/test_state_proofs_host.py): "SVC1", count, then per case the node count,
+  // each node as (length, bytes), the root, the key and the expected value as (length, bytes) and the
+  // status the host build gave
+  if (argc > 1) {
+    FILE* fh = fopen(argv[1], "rb");
+    char magic[4] = {0};
+    uint32_t n_cases = 0;
+    CHECK(fh && fread(magic, 1, 4, fh) == 4 && memcmp(magic, "SVC1", 4) == 0 && fread(&n_cases, 4, 1, fh) == 1);
+    auto bytes = [&](std::vector<uint8_t>& out) {
+      uint64_t len = 0;
+      bool ok = fread(&len, 8, 1, fh) == 1 && len < (1u << 20);
+      out.assign(ok ? len : 0, 0);
+      return ok && (len == 0 || fread(out.data(), 1, len, fh) == len);
+    };
+    uint32_t done = 0;
+    for (; fh && !g_fail && done < n_cases; ++done) {
+      uint64_t n_nodes = 0;
+      CHECK(fread(&n_nodes, 8, 1, fh) == 1 && n_nodes < 1024);
+      std::vector<std::vector<uint8_t>> nodes(g_fail ? 0 : n_nodes);
+      for (auto& node : nodes) CHECK(bytes(node));
+      std::vector<uint8_t> key, val;
+      uint32_t status = 0;
+      CHECK(fread(root, 1, 32, fh) == 32 && bytes(key) && bytes(val) && fread(&status, 4, 1, fh) == 1);
+      if (!g_fail) CHECK(walk(nodes, root, key, val) == status);
+    }
+    if (fh) fclose(fh);
+    if (!g_fail) printf("stateproofcheck: %u cases ok\n", done);
   }
   if (g_fail) {
     printf("stateproofcheck: %d failures\n", g_fail);

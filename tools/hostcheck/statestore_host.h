@@ -138,8 +138,8 @@ inline int prove(const View& v, const uint8_t* roots, const uint32_t* root_idx, 
     const uint32_t* ids = node_ids + q * max_nodes;
     uint64_t body;
     if (!pv::sg_pack_check(v.beg, v.end, v.n_nodes, ids, node_count[q], max_nodes, len, body)) continue;
-    const uint32_t hl = pv::rlp_list_header_len(body);
-    for (uint32_t k = 0; k < hl; ++k) proof_blob[o + k] = pv::rlp_list_header_byte(body, hl, k);
+    const uint32_t hl = pv::rlp_header_len(body);
+    for (uint32_t k = 0; k < hl; ++k) proof_blob[o + k] = pv::rlp_header_byte(192, body, hl, k);
     uint64_t w = o + hl;
     for (uint32_t k = node_count[q]; k-- > 0;) {
       const uint64_t b = v.beg[ids[k]], n = v.end[ids[k]] - b;
