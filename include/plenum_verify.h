@@ -514,6 +514,44 @@ int pv_state_store_pack_device(int32_t store, const uint32_t *node_ids, const ui
                                uint32_t max_nodes, const uint64_t *proof_off, uint64_t n_queries,
                                uint8_t *proof_blob, void *stream);
 
+/* Reads from the store (csrc/pv_trie_get.h): PruningState.get / get_for_root_hash
+ * (state/pruning_state.py:63-77) for a batch of keys at any roots the store holds -- the walk of
+ * pv_state_store_prove without the record of the nodes, so that a value of about a hundred bytes
+ * leaves the device and not the ~2 KB of proof around it.
+ *   pv_state_store_get      HOST buffers.  Query q: key q (key_blob / key_off) at root
+ *       roots[root_idx[q]] (32 bytes each; root_idx NULL: root q).  Writes, per query,
+ *         status   PV_SP_OK: the walk ended.  PV_SP_NODE_MISSING: the root or a referenced node is
+ *                  not in the store (the reference's KeyError).  PV_SP_MALFORMED: a node on the
+ *                  path is no trie node or, with decode, the stored value is not of the accepted
+ *                  form.  There is no max_nodes and no PV_SP_PATH_TOO_LONG.
+ *         found    1: the key has a value; 0: absent, or a status other than PV_SP_OK.  A blank
+ *                  root is PV_SP_OK with found = 0 and no lookup.
+ *         val_off  n_queries + 1 offsets into val_blob; value q is val_blob[val_off[q] ..
+ *                  val_off[q + 1]), empty unless found.  decode = 0: the value as the trie stores
+ *                  it, rlp([v]) (what get_value=True of a proof returns).  decode = 1: the payload
+ *                  PruningState.get_decoded returns, rlp_decode(value)[0] (:162-163).  found = 1
+ *                  with an empty value (a stored rlp([b''])) is a present key, not an absent one.
+ *       Accepted by decode: the stored value is one RLP list (short or long header) whose length
+ *       is the rest of the value and whose first item is a string (a byte below 0x80, a short
+ *       string, a long string); lengths are read leniently (no canonical-form check) and checked
+ *       against the value's range before use.  A bare string, an empty list, a first item that is
+ *       a list and any length that overruns are PV_SP_MALFORMED with found = 0.
+ *       With val_blob == NULL this is the sizing call: everything but the bytes is written.
+ *       With val_cap < val_off[n_queries]: PV_EINVAL before the copy launch, the text names both
+ *       numbers, and val_off and the per-query outputs are already written.
+ *       PV_EINVAL before any launch: key_off not monotone, root_idx[q] >= n_roots, decode not 0 or 1.
+ *   pv_state_store_get_device   the same with DEVICE buffers, read by the kernels only (key_off
+ *       and root_idx are not checked: a query whose root_idx is >= n_roots is PV_SP_MALFORMED);
+ *       val_off is scanned on the device and its last entry read back for the val_cap check.
+ *       roots 4-byte aligned.  Synchronous on `stream` (NULL = the library's). */
+int pv_state_store_get(int32_t store, const uint8_t *roots, const uint32_t *root_idx, uint64_t n_roots,
+                       const uint8_t *key_blob, const uint64_t *key_off, uint64_t n_queries, int32_t decode,
+                       uint8_t *status, uint8_t *found, uint64_t *val_off, uint8_t *val_blob, uint64_t val_cap);
+int pv_state_store_get_device(int32_t store, const uint8_t *roots, const uint32_t *root_idx, uint64_t n_roots,
+                              const uint8_t *key_blob, const uint64_t *key_off, uint64_t n_queries, int32_t decode,
+                              uint8_t *status, uint8_t *found, uint64_t *val_off, uint8_t *val_blob,
+                              uint64_t val_cap, void *stream);
+
 /* Pruning the store (csrc/pv_trie_prune.h): keep exactly the nodes reachable from the roots the
  * caller names, drop the rest and give the memory back.  It replaces what the reference's pruning
  * state does on commit and revertToHead (state/pruning_state.py:87-102): reference counts on every

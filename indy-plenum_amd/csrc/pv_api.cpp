@@ -295,7 +295,7 @@ void release_device(Device& d) {
   if (d.ws[1].stream) (void)hipStreamDestroy(d.ws[1].stream);
   for (auto& w : d.ws) w.stream = nullptr;
   d.pk.release(); d.sig.release(); d.blob.release(); d.verdict.release(); d.tamper.release(); d.stage.release();
-  d.off.release(); d.batch_off.release();
+  d.off.release(); d.batch_off.release(); d.vsrc.release();
   d.sender.release(); d.votes.release(); d.reached.release(); d.scan.release(); d.tflag.release(); d.tbits.release();
   d.ktab.release(); d.kidx.release(); d.kscr.release(); d.kscr2.release(); d.mk0.release(); d.mk1.release();
   d.kc.release(); d.kcpk.release();

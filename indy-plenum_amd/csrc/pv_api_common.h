@@ -389,6 +389,7 @@ struct Device {
   DevBuf<uint32_t> tflag, tbits;  // tally: out-of-range sender flag; staged voter bitmaps
   DevBuf<uint8_t> reached;
   DevBuf<uint64_t> scan;      // block sums of the device prefix scan
+  DevBuf<uint64_t> vsrc;      // pv_state_store_get_device: where each value lies in the store's blob
   DevBuf<uint32_t> ktab, kidx;  // prepared keys + per-signature key index (deduplicated host batches)
   DevBuf<uint32_t> kscr, kscr2;  // key-preparation scratch (kscr2: async slot 1)
   DevBuf<uint32_t> mk0, mk1;    // Merkle level ping-pong / leaf digests

@@ -1,8 +1,10 @@
 // The state-trie part of include/plenum_verify.h: pv_state_sort_device,
 // pv_state_build*, pv_state_update* and pv_state_apply* (the host sort, the
-// device sort, the build, sets and removals onto a committed root).
+// device sort, the build, sets and removals onto a committed root), and
+// pv_state_store_get* (reads at a root).
 #include "pv_api_common.h"
 #include "pv_trie_store.h"
+#include "pv_trie_get.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
 #include "pv_trie_sort.h"
@@ -796,6 +798,121 @@ int pv_state_apply(int32_t store, const uint8_t* old_root, const uint8_t* key_bl
                    uint64_t node_cap, uint8_t* digests) {
   return update_host_entry(store, old_root, key_blob, key_off, val_blob, val_off, n, insert, new_root, n_nodes,
                            n_bytes, node_blob, blob_cap, node_off, node_cap, digests, true);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- reads at a root
+namespace {
+
+// the walk and the scan of a read: status / found / src / val_off (scanned) are device memory
+int get_walk(StateStore& st, Device& d, hipStream_t s, const uint8_t* roots, const uint32_t* root_idx, uint64_t n_roots,
+             const uint8_t* key_blob, const uint64_t* key_off, uint64_t n_queries, bool decode, uint8_t* status,
+             uint8_t* found, uint64_t* src, uint64_t* val_off) {
+  HIP_OK(d.scan.ensure(pv::scan_sums_words(n_queries + 1)));
+  HIP_OK(pv::launch_trie_get(st.blob, st.beg, st.end, st.dig, st.table, st.slots, (uint32_t)st.n_nodes, w32(roots),
+                             root_idx, n_roots, key_blob, key_off, n_queries, decode, status, found, src, val_off,
+                             merkle_blocks(d), s));
+  HIP_OK(pv::launch_exclusive_scan(val_off, n_queries + 1, d.scan.p, s));
+  return PV_OK;
+}
+
+int cap_refusal(uint64_t val_cap, uint64_t total) {
+  return fail(PV_EINVAL, "val_cap %llu is below the %llu bytes of the values", (unsigned long long)val_cap,
+              (unsigned long long)total);
+}
+
+}  // namespace
+
+extern "C" {
+
+// PruningState.get / get_for_root_hash per key (state/pruning_state.py:63-77; with decode,
+// get_decoded, :162-163; Trie._get, state/trie/pruning_trie.py:376-407) as one batch at any roots
+// the store holds; see include/plenum_verify.h.
+int pv_state_store_get(int32_t store, const uint8_t* roots, const uint32_t* root_idx, uint64_t n_roots,
+                       const uint8_t* key_blob, const uint64_t* key_off, uint64_t n_queries, int32_t decode,
+                       uint8_t* status, uint8_t* found, uint64_t* val_off, uint8_t* val_blob, uint64_t val_cap) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_queries == 0) return PV_OK;
+  if (!roots || !key_off || !status || !found || !val_off) return fail(PV_EINVAL, "null buffer");
+  if (decode != 0 && decode != 1) return fail(PV_EINVAL, "decode must be 0 or 1");
+  if (n_roots == 0) return fail(PV_EINVAL, "queries without roots");
+  if (n_queries > (1ull << 40)) return fail(PV_EINVAL, "more than 2^40 queries in one call");
+  if (!root_idx && n_roots < n_queries)
+    return fail(PV_EINVAL, "%llu roots for %llu queries without root_idx", (unsigned long long)n_roots,
+                (unsigned long long)n_queries);
+  Ragged keys(key_off, n_queries);
+  if (const int rc = keys.check("key_off")) return rc;
+  if (keys.len && !key_blob) return fail(PV_EINVAL, "null buffer");
+  if (root_idx)
+    for (uint64_t i = 0; i < n_queries; ++i)
+      if (root_idx[i] >= n_roots)
+        return fail(PV_EINVAL, "root_idx[%llu] = %u is not below n_roots %llu", (unsigned long long)i, root_idx[i],
+                    (unsigned long long)n_roots);
+  if (const int rc = en.begin()) return rc;
+  Device& d = *en.d;
+  hipStream_t s = en.s;
+  TmpBuf<uint8_t> droots, dkeys, dstatus, dfound, dvals;
+  TmpBuf<uint32_t> dridx;
+  TmpBuf<uint64_t> dkoff, dsrc, dvoff;
+  StreamDrain tail{s};
+  HIP_OK(droots.put(roots, n_roots * 32, s));
+  if (root_idx) HIP_OK(dridx.put(root_idx, n_queries, s));
+  HIP_OK(dkeys.alloc(keys.len + 4));
+  if (keys.len) HIP_OK(hipMemcpyAsync(dkeys.p, key_blob + keys.b0, keys.len, hipMemcpyHostToDevice, s));
+  HIP_OK(dkoff.put(keys.rebased(), n_queries + 1, s));
+  HIP_OK(dstatus.alloc(n_queries));
+  HIP_OK(dfound.alloc(n_queries));
+  HIP_OK(dsrc.alloc(n_queries));
+  HIP_OK(dvoff.alloc(n_queries + 1));
+  if (const int rc = get_walk(*st, d, s, droots.p, root_idx ? dridx.p : nullptr, n_roots, dkeys.p, dkoff.p, n_queries,
+                              decode != 0, dstatus.p, dfound.p, dsrc.p, dvoff.p))
+    return rc;
+  HIP_OK(hipMemcpyAsync(status, dstatus.p, n_queries, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(found, dfound.p, n_queries, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(val_off, dvoff.p, (n_queries + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  const uint64_t total = val_off[n_queries];
+  if (!val_blob) return tail.finish();   // the sizing call
+  if (val_cap < total) return cap_refusal(val_cap, total);
+  if (total == 0) return tail.finish();
+  HIP_OK(dvals.alloc(total));
+  HIP_OK(pv::launch_trie_get_copy(st->blob, dsrc.p, dvoff.p, n_queries, dvals.p, merkle_blocks(d), s));
+  HIP_OK(hipMemcpyAsync(val_blob, dvals.p, total, hipMemcpyDeviceToHost, s));
+  return tail.finish();
+}
+
+// The same read (state/pruning_state.py:63-77, 162-163) over DEVICE buffers, which only the
+// kernels read: key_off and root_idx are not checked here; see include/plenum_verify.h.
+int pv_state_store_get_device(int32_t store, const uint8_t* roots, const uint32_t* root_idx, uint64_t n_roots,
+                              const uint8_t* key_blob, const uint64_t* key_off, uint64_t n_queries, int32_t decode,
+                              uint8_t* status, uint8_t* found, uint64_t* val_off, uint8_t* val_blob, uint64_t val_cap,
+                              void* stream) {
+  Entry en;
+  StateStore* st;
+  if (const int rc = store_enter(en, store, &st)) return rc;
+  if (n_queries == 0) return PV_OK;
+  if (!roots || !key_blob || !key_off || !status || !found || !val_off) return fail(PV_EINVAL, "null device buffer");
+  if (decode != 0 && decode != 1) return fail(PV_EINVAL, "decode must be 0 or 1");
+  if (n_roots == 0) return fail(PV_EINVAL, "queries without roots");
+  if (n_queries > (1ull << 40)) return fail(PV_EINVAL, "more than 2^40 queries in one call");
+  if (reinterpret_cast<uintptr_t>(roots) & 3u) return fail(PV_EINVAL, "roots must be 4-byte aligned");
+  if (const int rc = en.begin(stream)) return rc;
+  Device& d = *en.d;
+  HIP_OK(d.vsrc.ensure(n_queries));
+  if (const int rc = get_walk(*st, d, en.s, roots, root_idx, n_roots, key_blob, key_off, n_queries, decode != 0, status,
+                              found, d.vsrc.p, val_off))
+    return rc;
+  uint64_t total = 0;
+  HIP_OK(hipMemcpyAsync(&total, val_off + n_queries, 8, hipMemcpyDeviceToHost, en.s));
+  HIP_OK(hipStreamSynchronize(en.s));
+  if (!val_blob) return PV_OK;   // the sizing call
+  if (val_cap < total) return cap_refusal(val_cap, total);
+  if (total == 0) return PV_OK;
+  HIP_OK(pv::launch_trie_get_copy(st->blob, d.vsrc.p, val_off, n_queries, val_blob, merkle_blocks(d), en.s));
+  return en.finish();
 }
 
 }  // extern "C"

@@ -245,6 +245,19 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
                                   const uint64_t* proof_off, uint64_t n_queries, uint8_t* proof_blob, int max_blocks,
                                   hipStream_t s);
 
+// Reads from the resident store (pv_trie_get.h); all device memory.
+//   trie_get       one query per lane: status, found, src[q] (where the value lies in the store's
+//                  blob) and val_off[q] <- the value's length, val_off[n_queries] <- 0; the caller
+//                  scans val_off (n_queries + 1) in place
+//   trie_get_copy  TG_GROUP lanes per value: val_blob[val_off[q] ..] <- the value's bytes
+hipError_t launch_trie_get(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                           const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t* roots,
+                           const uint32_t* root_idx, uint64_t n_roots, const uint8_t* key_blob,
+                           const uint64_t* key_off, uint64_t n_queries, bool decode, uint8_t* status, uint8_t* found,
+                           uint64_t* src, uint64_t* val_off, int max_blocks, hipStream_t s);
+hipError_t launch_trie_get_copy(const uint8_t* blob, const uint64_t* src, const uint64_t* val_off, uint64_t n_queries,
+                                uint8_t* val_blob, int max_blocks, hipStream_t s);
+
 // Pruning the resident store (pv_trie_prune.h); all device memory.
 //   trie_prune_seed   one lane per kept root: status[i], the root's node marked and enqueued
 //   trie_prune_level  one lane per queue entry head .. tail - 1: tp_expand (children marked, the

@@ -20,6 +20,7 @@
 #include "pv_sha3.h"
 #include "pv_trie_proof.h"
 #include "pv_trie_store.h"
+#include "pv_trie_get.h"
 #include "pv_trie_prune.h"
 #include "pv_trie_build.h"
 #include "pv_trie_update.h"
@@ -1882,6 +1883,73 @@ hipError_t launch_trie_proof_pack(const uint8_t* blob, const uint64_t* beg, cons
   if (n_queries == 0) return hipSuccess;
   hipLaunchKernelGGL(k_trie_proof_pack, dim3(mp_grid(n_queries * 64, max_blocks)), dim3(256), 0, s, blob, beg,
                      end, n_nodes, node_ids, node_count, max_nodes, proof_off, n_queries, proof_blob);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- reads from the resident store
+// pv_trie_get.h.  One query per lane, as k_trie_prove; val_off[i] <- the length of value i and
+// val_off[n] <- 0 (what the exclusive scan takes), src[i] <- where value i lies in the blob.
+__global__ __launch_bounds__(256) void k_trie_get(
+    const uint8_t* __restrict__ blob, const uint64_t* __restrict__ beg, const uint64_t* __restrict__ end,
+    const uint32_t* __restrict__ dig, const uint32_t* __restrict__ table, uint32_t slots, uint32_t n_nodes,
+    const uint32_t* __restrict__ roots, const uint32_t* __restrict__ root_idx, uint64_t n_roots,
+    const uint8_t* __restrict__ key_blob, const uint64_t* __restrict__ key_off, uint64_t n, uint32_t decode,
+    uint8_t* __restrict__ status, uint8_t* __restrict__ found, uint64_t* __restrict__ src,
+    uint64_t* __restrict__ val_off) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i <= n; i += stride) {
+    if (i == n) {
+      val_off[n] = 0;
+      break;
+    }
+    const uint64_t p = root_idx ? root_idx[i] : i;
+    TgResult r;
+    r.status = SP_MALFORMED;
+    r.found = 0;
+    r.beg = r.len = 0;
+    if (p < n_roots) {
+      uint32_t rt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) rt[k] = roots[8 * p + k];
+      const uint64_t ko = key_off[i];
+      tg_get(blob, beg, end, dig, table, slots, n_nodes, rt, key_blob + ko, key_off[i + 1] - ko, decode != 0, r);
+    }
+    status[i] = (uint8_t)r.status;
+    found[i] = (uint8_t)r.found;
+    src[i] = r.beg;
+    val_off[i] = r.len;
+  }
+}
+
+// TG_GROUP lanes per value: 64 / TG_GROUP values per wave, each group strides over its value's bytes.
+__global__ __launch_bounds__(256) void k_trie_get_copy(const uint8_t* __restrict__ blob,
+                                                        const uint64_t* __restrict__ src,
+                                                        const uint64_t* __restrict__ val_off, uint64_t n,
+                                                        uint8_t* __restrict__ out) {
+  constexpr uint32_t per_block = 256 / TG_GROUP;
+  const uint32_t lane = threadIdx.x % TG_GROUP;
+  const uint64_t stride = (uint64_t)gridDim.x * per_block;
+  for (uint64_t q = (uint64_t)blockIdx.x * per_block + threadIdx.x / TG_GROUP; q < n; q += stride)
+    tg_copy_group(blob, src, val_off, q, lane, out);
+}
+
+hipError_t launch_trie_get(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                           const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t* roots,
+                           const uint32_t* root_idx, uint64_t n_roots, const uint8_t* key_blob,
+                           const uint64_t* key_off, uint64_t n_queries, bool decode, uint8_t* status, uint8_t* found,
+                           uint64_t* src, uint64_t* val_off, int max_blocks, hipStream_t s) {
+  if (n_queries == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_get, dim3(mp_grid(n_queries + 1, max_blocks)), dim3(256), 0, s, blob, beg, end, dig, table,
+                     slots, n_nodes, roots, root_idx, n_roots, key_blob, key_off, n_queries, decode ? 1u : 0u, status,
+                     found, src, val_off);
+  return hipGetLastError();
+}
+
+hipError_t launch_trie_get_copy(const uint8_t* blob, const uint64_t* src, const uint64_t* val_off, uint64_t n_queries,
+                                uint8_t* val_blob, int max_blocks, hipStream_t s) {
+  if (n_queries == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_trie_get_copy, dim3(mp_grid(n_queries * TG_GROUP, max_blocks)), dim3(256), 0, s, blob, src,
+                     val_off, n_queries, val_blob);
   return hipGetLastError();
 }
 

@@ -138,10 +138,13 @@ struct SgResult {
 
 // The generation walk for one (root, key).  ids[0 .. min(node_count, max_nodes))
 // receives the hashed nodes' ids, root first; ids goes straight to the caller's
-// (global) memory, so no per-lane array is indexed at run time.
-PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
-                   const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t root[8],
-                   const uint8_t* key, uint64_t klen, uint32_t* ids, uint32_t max_nodes, SgResult& r) {
+// (global) memory, so no per-lane array is indexed at run time.  RECORD false is
+// the read of pv_trie_get.h: the same descent, ids and max_nodes are not looked
+// at, and no walk is SP_PATH_TOO_LONG.
+template <bool RECORD>
+PV_HD void sg_walk_t(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                     const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t root[8],
+                     const uint8_t* key, uint64_t klen, uint32_t* ids, uint32_t max_nodes, SgResult& r) {
   r.status = SP_OK;
   r.node_count = 0;
   r.body_len = r.last_beg = r.val_beg = r.val_len = 0;
@@ -152,7 +155,7 @@ PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end
     return;
   }
   uint64_t cb = beg[j], ce = end[j];   // the current node's RLP
-  if (max_nodes) ids[0] = j;
+  if (RECORD && max_nodes) ids[0] = j;
   r.node_count = 1;
   r.body_len = ce - cb;
   r.last_beg = cb;
@@ -183,13 +186,19 @@ PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end
     }
     cb = beg[j];
     ce = end[j];
-    if (r.node_count < max_nodes) ids[r.node_count] = j;
+    if (RECORD && r.node_count < max_nodes) ids[r.node_count] = j;
     ++r.node_count;   // counted on above max_nodes, without storing
     r.body_len += ce - cb;
     r.last_beg = cb;
   }
-  if (st == SP_OK && r.node_count > max_nodes) st = SP_PATH_TOO_LONG;
+  if (RECORD && st == SP_OK && r.node_count > max_nodes) st = SP_PATH_TOO_LONG;
   r.status = st;
+}
+
+PV_HD void sg_walk(const uint8_t* blob, const uint64_t* beg, const uint64_t* end, const uint32_t* dig,
+                   const uint32_t* table, uint32_t slots, uint32_t n_nodes, const uint32_t root[8],
+                   const uint8_t* key, uint64_t klen, uint32_t* ids, uint32_t max_nodes, SgResult& r) {
+  sg_walk_t<true>(blob, beg, end, dig, table, slots, n_nodes, root, key, klen, ids, max_nodes, r);
 }
 
 // What a query's outputs are, from its walk: the serialized length (list header

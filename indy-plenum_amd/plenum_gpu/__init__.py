@@ -24,8 +24,10 @@ runs on HIP kernels through the C-ABI library libplenum_verify.so:
                   state/pruning_state.py, state/trie/pruning_trie.py
   state_store     GpuStateStore: a device-resident trie node store,
                   generate_state_proof (+ generate_state_proofs_batch), build_state,
-                  state_root_batch
+                  state_root_batch, get_batch (reads)
                   state/pruning_state.py, state/trie/pruning_trie.py
+  pruning_state   GpuPruningState: the State interface over the store (set / remove /
+                  headHash / commit / revertToHead / get)           state/pruning_state.py
   serialization, base58, exceptions, constants   the data formats either side
 
 device.py holds the device-resident (torch tensor) entry points; _native.py is
@@ -38,7 +40,8 @@ _MERKLE_PROOFS = ('GpuMerkleVerifier', 'GpuMerkleTree', 'STH')
 _LEDGER_TREE = ('GpuLedgerTree',)
 _STATE_PROOFS = ('GpuStateVerifier', 'verify_state_proofs_batch', 'sha3_256_batch')
 _STATE_STORE = ('GpuStateStore', 'state_root_batch')
-__all__ = list(_MERKLE_PROOFS + _LEDGER_TREE + _STATE_PROOFS + _STATE_STORE)
+_PRUNING_STATE = ('GpuPruningState',)
+__all__ = list(_MERKLE_PROOFS + _LEDGER_TREE + _STATE_PROOFS + _STATE_STORE + _PRUNING_STATE)
 
 
 def __getattr__(name):
@@ -54,4 +57,7 @@ def __getattr__(name):
     if name in _STATE_STORE:
         from . import state_store
         return getattr(state_store, name)
+    if name in _PRUNING_STATE:
+        from . import pruning_state
+        return getattr(pruning_state, name)
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -177,6 +177,13 @@ SIGNATURES = [
       _vp, _vp]),
     ('pv_state_store_pack_device', ctypes.c_int,
      [ctypes.c_int32, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp]),
+    # reads at a root: HOST buffers, and the same with DEVICE buffers and a stream
+    ('pv_state_store_get', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_int32, _vp, _vp, _vp, _vp,
+      ctypes.c_uint64]),
+    ('pv_state_store_get_device', ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_int32, _vp, _vp, _vp, _vp,
+      ctypes.c_uint64, _vp]),
     ('pv_verify_keyed_device', ctypes.c_int,
      [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_int, _vp]),
     ('pv_time_verify_keyed_device', ctypes.c_int,

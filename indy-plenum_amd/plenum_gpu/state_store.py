@@ -66,7 +66,16 @@ reference would return [b''].
   `apply_batch_sha256(root, items)` hashes NYM-style preimages into the key buffer on the device
   first, so no key crosses back to the host.
 
-Out of scope: generate_state_proof_for_keys_with_prefix (a subtree traversal).
+* `GpuStateStore.get_batch([(root, key), ...], decode=True)` -- pv_state_store_get: reads,
+  PruningState.get / get_for_root_hash (state/pruning_state.py:63-77).  One lane per query walks as
+  a proof does but records no node (k_trie_get), a scan lays the values out and a lane group per
+  value gathers them (k_trie_get_copy): the values alone cross to the host, not the proofs around
+  them.  `get_host(db, root, key, decode)` is the pure-Python mirror.  `get_for_root_hash_batch`
+  still goes through the proofs.  plenum_gpu.pruning_state.GpuPruningState is the reference's State
+  interface (set / remove / headHash / commit / revertToHead / get) over a store.
+
+Out of scope: generate_state_proof_for_keys_with_prefix, as_dict and
+get_all_leaves_for_root_hash (subtree traversals).
 """
 import ctypes
 import hashlib
@@ -205,6 +214,34 @@ def walk_host(db, root, key, max_nodes=None):
         nodes.append(blob)
         cb, ce = 0, len(blob)
     return end(PV_SP_MALFORMED)
+
+
+def decode_value_host(value):
+    """tg_decode of csrc/pv_trie_get.h: the stored value -> the payload of its first item, or None
+    unless the value is one RLP list that fills it and whose first item is a string"""
+    head = _rlp_item(value, 0, len(value))
+    if head is None or not head[0] or head[2] != len(value):
+        return None
+    first = _rlp_item(value, head[1], head[2])
+    if first is None or first[0]:
+        return None
+    return bytes(value[first[1]:first[2]])
+
+
+def get_host(db, root, key, decode=True):
+    """tg_get of csrc/pv_trie_get.h in Python over `db` = {sha3(node RLP): node RLP} -> (status,
+    found, value): the walk of walk_host without a bound on the nodes; found is False for an
+    absent key, a blank root and every status but PV_SP_OK; with decode the value is the payload
+    PruningState.get_decoded returns, and a stored value of another form is PV_SP_MALFORMED."""
+    st, _, value, _, _ = walk_host(db, root, key)
+    if st != PV_SP_OK or not value:
+        return st, False, b''
+    if not decode:
+        return PV_SP_OK, True, value
+    payload = decode_value_host(value)
+    if payload is None:
+        return PV_SP_MALFORMED, False, b''
+    return PV_SP_OK, True, payload
 
 
 def _node_children(blob, cb, ce, depth=0):
@@ -894,6 +931,42 @@ class Proved:
         return self.blob[o:o + int(self.val_len[q])].tobytes()
 
 
+class Got:
+    """The arrays of one pv_state_store_get call."""
+    __slots__ = ('status', 'found', 'val_off', 'blob')
+
+    def value(self, q):
+        """the value of query q (b'' for a present key with an empty payload), None unless found"""
+        if not self.found[q]:
+            return None
+        return self.blob[int(self.val_off[q]):int(self.val_off[q + 1])].tobytes()
+
+    def values(self):
+        """every query's value; KeyError where the reference raises it (the root or a node on the
+        path is not in the store), ValueError for a node or a stored value that is not well formed"""
+        out = []
+        for q in range(len(self.status)):
+            st = int(self.status[q])
+            if st == PV_SP_NODE_MISSING:
+                raise KeyError('item {}: the root or a node on the path is not in the store'.format(q))
+            if st != PV_SP_OK:
+                raise ValueError('item {}: a node on the path or the stored value is not well formed'.format(q))
+            out.append(self.value(q))
+        return out
+
+
+def group_roots(items):
+    """[(root, key), ...] -> (distinct root hashes, root index per item, keys as bytes)"""
+    index, roots, ridx, keys = {}, [], [], []
+    for root, key in items:
+        rh = root_hash_of(root)
+        ridx.append(index.setdefault(rh, len(index)))
+        if ridx[-1] == len(roots):
+            roots.append(rh)
+        keys.append(key.encode() if isinstance(key, str) else bytes(key))
+    return roots, ridx, keys
+
+
 class GpuStateStore:
     """A device-resident store of trie nodes keyed by their SHA3-256: append-only between two
     prune() calls, each of which keeps the nodes reachable from the roots it is given."""
@@ -1130,6 +1203,87 @@ class GpuStateStore:
             else:
                 out.append((pr.proof(q), rlp_decode(pr.value(q))[0] if pr.val_len[q] else None))
         return out
+
+    def get(self, roots, root_idx, keys, decode=True, val_cap=None):
+        """pv_state_store_get: `roots` 32-byte hashes, root_idx per key (None: root q for key q)
+        -> Got.  The values' bytes are sized by a first call unless val_cap is given."""
+        keys = [bytes(k) for k in keys]
+        n = len(keys)
+        out = Got()
+        out.status, out.found = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        out.val_off = np.zeros(n + 1, np.uint64)
+        out.blob = np.zeros(0, np.uint8)
+        if n == 0:
+            return out
+        rts = np.frombuffer(b''.join(bytes(r) for r in roots), np.uint8)
+        ridx = None if root_idx is None else np.ascontiguousarray(root_idx, np.uint32)
+        kblob, koff = nat.pack_messages(keys)
+        cap = max(1 << 12, 160 * n) if val_cap is None else val_cap
+        for _ in range(2):
+            blob = np.empty(max(cap, 1), np.uint8)
+            rc = self._lib.pv_state_store_get(self._id, _p(rts), _p(ridx), len(roots), _p(kblob), _p(koff), n,
+                                              int(decode), _p(out.status), _p(out.found), _p(out.val_off), _p(blob),
+                                              cap)
+            total = int(out.val_off[n])
+            # a capacity guessed too small: the offsets are written, the bytes are not
+            if rc == 0 or val_cap is not None or total <= cap or \
+                    not self._lib.pv_last_error().startswith(b'val_cap '):
+                break
+            cap = total
+        nat._check('pv_state_store_get', rc)
+        out.blob = blob[:total]
+        return out
+
+    def get_batch(self, items, decode=True):
+        """PruningState.get_for_root_hash (state/pruning_state.py:72-77) for [(root, key), ...] in one
+        pv_state_store_get call -> the values (decoded as get_decoded does, :162-163, or with
+        decode=False as the trie stores them), None for an absent key; b'' is a present key with an
+        empty payload.  KeyError where the reference raises it: the root or a node on the path is
+        not in the store; ValueError for a node or a stored value that is not well formed."""
+        items = list(items)
+        roots, ridx, keys = group_roots(items)
+        got = self.get(roots, ridx, keys, decode)
+        return got.values()
+
+    def get_batch_sha256(self, root, preimages, decode=True):
+        """get_batch at one root for keys that are sha256(preimage) (nym_to_state_key,
+        plenum/server/request_handlers/utils.py:38-39): pv_sha256_batch_device hashes the preimages
+        into the device key buffer pv_state_store_get_device walks, so no key crosses back to the
+        host and only the values do."""
+        import torch
+        nat.ensure_init()
+        preimages = [p.encode() if isinstance(p, str) else bytes(p) for p in preimages]
+        n = len(preimages)
+        if n == 0:
+            return []
+        pblob, poff = nat.pack_messages(preimages)
+        d_pb, d_po = _upload(pblob, self.device), _upload(poff, self.device)
+        dev = d_pb.device
+        d_keys = torch.zeros(32 * n + 16, dtype=torch.uint8, device=dev)
+        d_ko = _upload(32 * np.arange(n + 1, dtype=np.uint64), self.device)
+        d_root = _upload(np.frombuffer(root_hash_of(root), np.uint8), self.device)
+        d_ridx = torch.zeros(4 * n, dtype=torch.uint8, device=dev)
+        d_status, d_found = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
+        d_voff = torch.zeros(8 * (n + 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)   # the library runs on its own stream
+        nat._check('pv_sha256_batch_device', self._lib.pv_sha256_batch_device(_dp(d_pb), _dp(d_po), n, -1, _dp(d_keys),
+                                                                            self.device, None))
+        cap = max(1 << 12, 160 * n)
+        for _ in range(2):
+            d_vals = torch.zeros(cap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            rc = self._lib.pv_state_store_get_device(self._id, _dp(d_root), _dp(d_ridx), 1, _dp(d_keys), _dp(d_ko), n,
+                                                     int(decode), _dp(d_status), _dp(d_found), _dp(d_voff),
+                                                     _dp(d_vals), cap, None)
+            if rc == 0 or not self._lib.pv_last_error().startswith(b'val_cap '):
+                break
+            cap = int(d_voff.cpu().numpy().view(np.uint64)[n])
+        nat._check('pv_state_store_get_device', rc)
+        got = Got()
+        got.status, got.found = d_status.cpu().numpy(), d_found.cpu().numpy()
+        got.val_off = d_voff.cpu().numpy().view(np.uint64)
+        got.blob = d_vals.cpu().numpy()[:int(got.val_off[n])]
+        return got.values()
 
     def get_for_root_hash_batch(self, items):
         """PruningState.get_for_root_hash (state/pruning_state.py:72-77) for [(root, key), ...]:
